@@ -6,13 +6,19 @@ resident in HBM: row norms + regulariser, N x N kernel build, float32 MFMA Chole
 on the float64 kernel, and the posterior (cross kernel, mean, diag variance) for M test queries.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3|cfg2|cfg4|cfg5|cfg1] [--mode shard|shard32|replicate|grid2d]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline (value, ms_per_step, dtype, config).
+--dump-outputs DIR writes what the last timed step returned (posterior mean and variance) as float64 DIR/<name>.npy.
+--full adds what the headline does not need: per-stage events and per-kernel timers in the timed steps (they synchronise
+after every step), the rooflines, fit_info, the CPU baseline on one GPU and the comparison legs on several.
 
 N = 1: configs[2] (cfg3, N = 32768, the north-star size).  N > 1 (launched by torch.distributed.run, one rank per GPU):
 configs[3] (cfg4, N = 65536) in the layout BASELINE.json's north star names -- rank g builds the row block
 [g N/G, (g+1) N/G) of the float64 kernel, ONE in-place RCCL all-gather over xGMI completes K on every rank
 (nngp_allgather_rows of the C ABI; torch.distributed's nccl all_gather_into_tensor if the library's own communicator
 cannot be created), then the 1-D block-cyclic Cholesky (one broadcast per block column), replicated alpha solve, test
-rows sharded.  "Strong" scaling: the problem is fixed.  The line also carries the three numbers SURVEY.md 8e asks for
+rows sharded.  "Strong" scaling: the problem is fixed.  With --full the line also carries the three numbers SURVEY.md 8e asks for
 -- sharded build, all-gather, replicated full build -- and, measured after the timed steps in the same invocation,
 the step time of the "replicate" layout (every rank runs the whole fit, no data-path collective) for comparison.
 Rank 0 prints ONE JSON line.
@@ -124,6 +130,14 @@ def cpu_baseline(n_bench, d, m, n_relu, gpu_ms):
     return out
 
 
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: the arrays the timed path returned in its last step, as float64 DIR/<name>.npy.  The inputs come from
+    fixed seeds, so two builds run with the same arguments can be compared output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def bench_grid2d(args, world, rank, dev, cfg_name, x, y, xt, n, d, n_relu, get, m, desc):
     """Opt-in comparison layout: the 2-D block-cyclic fit of nngp-src_amd/dist2d.py.  A step = build of the
     rank's own tiles + distributed Cholesky + distributed CG for alpha + mean and level-1 variance of the test queries (replicated
@@ -139,16 +153,17 @@ def bench_grid2d(args, world, rank, dev, cfg_name, x, y, xt, n, d, n_relu, get, 
 
     def step():
         gp = dist2d.Dist2DGP(ops, grid, x, y, diag_reg=1e-3, nb=1024).fit()
-        gp.predict(xt[:mt])
-        return gp
+        return gp, gp.predict(xt[:mt])
 
     for _ in range(args.warmup):
         step()
     dist.barrier(); torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        gp = step()
+        gp, out = step()
     dist.barrier(); torch.cuda.synchronize()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"mean": out[0], "var": out[1]})
     t = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     if rank == 0:
@@ -184,8 +199,7 @@ def bench_shard32(args, world, rank, dev, cfg_name, x, y, xt, n, d, n_relu, get,
 
     def step():
         gp = shard32.RowShardedGP(ops, x, y, distributed_cholesky=dchol).fit()
-        gp.predict(xt, cov=True)
-        return gp
+        return gp, gp.predict(xt, cov=True)
 
     for _ in range(args.warmup):
         step()
@@ -194,10 +208,12 @@ def bench_shard32(args, world, rank, dev, cfg_name, x, y, xt, n, d, n_relu, get,
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        gp = step()
+        gp, out = step()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"mean": out[0], "var": out[1]})
     t = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -306,9 +322,16 @@ def main():
     ap.add_argument("--mode", default=os.environ.get("NNGP_DIST_MODE", "shard"), choices=["shard", "replicate", "grid2d", "shard32"],
                     help="multi-GPU layout (default: the north star's row-block shard + all-gather; grid2d: the 2-D block-cyclic "
                          "fit of dist2d.py, no rank holding the whole kernel or factor)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-compare", action="store_true", help="multi-GPU: skip the untimed comparison legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: per-stage and per-kernel timings with their "
+                         "rooflines, fit_info, the CPU baseline (one GPU) and the comparison legs (several GPUs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-compare", action="store_true", help="--full, multi-GPU: skip the untimed comparison legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (posterior mean and variance, float64) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args.gpus)  # no torch import, no GPU call before this point
 
@@ -431,9 +454,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return [float(v) for v in t.tolist()]
 
-    # live timing of the dominant kernel (k_gemm_nt_h3, the Cholesky's split-float16 trailing update) for `roofline`
+    # --full: live timing of the dominant kernel (k_gemm_nt_h3, the Cholesky's split-float16 trailing update) for `roofline`
     ktimer = {"on": False, "launches": 0, "ms": 0.0, "flops": 0.0, "bytes": 0.0}
-    if not (shard and dist_chol):
+    if args.full and not (shard and dist_chol):
         try:
             model.update_timer(True)
             ktimer["on"] = True
@@ -441,18 +464,20 @@ def main():
             pass
     # ... and of the posterior's residual products on the int8 pipe (k_gemm_nt_i8s) for `roofline_residual`
     rtimer = {"on": False, "launches": 0, "ms": 0.0, "flops": 0.0, "ops": 0.0}
-    try:
-        model.residual_timer(True)
-        rtimer["on"] = True
-    except _lib.NngpError:
-        pass
+    if args.full:
+        try:
+            model.residual_timer(True)
+            rtimer["on"] = True
+        except _lib.NngpError:
+            pass
     # ... and of the posterior's blocked triangular solves for `roofline_solves`
     stimer = {"on": False, "solves": 0, "ms": 0.0, "flops": 0.0}
-    try:
-        model.trsm_timer(True)
-        stimer["on"] = True
-    except _lib.NngpError:
-        pass
+    if args.full:
+        try:
+            model.trsm_timer(True)
+            stimer["on"] = True
+        except _lib.NngpError:
+            pass
     for _ in range(args.warmup):
         step()
     barrier()
@@ -460,13 +485,53 @@ def main():
         model.residual_timer_read()  # drop the warm-up launches
     if stimer["on"]:
         model.trsm_timer_read()
-    stages = {}
+    stages = {} if args.full else None  # --full: events around every stage, which also synchronises after every step
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step(stages)
+        out = step(stages)
     barrier()
     elapsed = time.perf_counter() - t0
     (elapsed,) = max_over_ranks([elapsed])
+
+    if args.dump_outputs:  # the test rows are dealt to the ranks in order; rank 0 writes all of them
+        mine = None if out is None else [t.cpu().numpy() for t in out]
+        parts = [mine]
+        if world > 1:
+            parts = [None] * world
+            dist.all_gather_object(parts, mine)
+        parts = [p for p in parts if p is not None]
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"mean": np.concatenate([p[0] for p in parts]), "var": np.concatenate([p[1] for p in parts])})
+
+    fl = flop_model(n, d, m, n_relu)
+    ms = elapsed / args.steps * 1e3
+    result = {
+        "metric": "NNGP kernel-build + GP-solve wall-clock (ms) and GFLOP/s at N train queries",
+        "value": round(fl["total"] / (ms * 1e-3) / 1e9, 2), "unit": "GFLOP/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3),
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+        "dtype": "f32 (Cholesky products as split f16 x3, f32 accumulate; f64 build/CG/means; the posterior's float64-grade residual as exact int8 digit-plane products)", "data": "synthetic",
+        "config": {"workload": desc, "N": n, "d": d, "n_relu": n_relu, "get": get, "M_test": m,
+                   "parallelism": ("single GPU" if world == 1 else
+                                   ("row-block kernel shard x%d + one in-place all-gather, %s, replicated alpha solve, test rows sharded"
+                                    % (world, "block-cyclic Cholesky (broadcast per block column)" if dist_chol else "replicated Cholesky")) if shard else
+                                   "fit replicated on %d GPUs (no data-path collective), test rows sharded" % world),
+                   "precision": "float64 kernel build + CG residual; float32 Cholesky (preconditioner) whose trailing updates run "
+                                "as split-float16 MFMA products (hi+lo, 3 per term, float32 accumulate); float64 means; variances: "
+                                "float32-grade solves on the float16 pipe + one float64-GRADE residual product on the int8 pipe "
+                                "(operands cut into exact 8-bit digit planes, 12 exact plane products, float64 combination; level 1)"},
+    }
+    if world > 1:
+        result["shard"] = ({"ranks_seen": ranks_seen, "collective": collective} if shard else
+                           {"ranks_seen": ranks_seen, "note": "replicate layout: no data-path collective"})
+    if not args.full:  # a plain run: the headline only
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if comm is not None:
+            comm.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     info = model.info()
     alpha_l2 = float(torch.linalg.vector_norm(model.alpha()).item())
@@ -530,28 +595,12 @@ def main():
         _t = _pm.get("kernels", {}).get("k_trsm_tickets")
         t_traffic = (_t["fetch_bytes"] + _t["write_bytes"]) / _t["calls"] if _t and _t.get("calls") else None
     if rank == 0:
-        fl = flop_model(n, d, m, n_relu)
-        ms = elapsed / args.steps * 1e3
         chol_tflops = fl["cholesky"] / (st["cholesky"] * 1e-3) / 1e12
         post_ms = st["posterior"] + st["alpha_solve"]
         post_tflops = fl["posterior"] / (post_ms * 1e-3) / 1e12
         k_bytes = (8 * n * n + 8 * n * d) * (1 if world == 1 or not shard else 1.0 / world)
         k_gbps = k_bytes / (st["kernel_build"] * 1e-3) / 1e9
-        result = {
-            "metric": "NNGP kernel-build + GP-solve wall-clock (ms) and GFLOP/s at N train queries",
-            "value": round(fl["total"] / (ms * 1e-3) / 1e9, 2), "unit": "GFLOP/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3),
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": "f32 (Cholesky products as split f16 x3, f32 accumulate; f64 build/CG/means; the posterior's float64-grade residual as exact int8 digit-plane products)", "data": "synthetic",
-            "config": {"workload": desc, "N": n, "d": d, "n_relu": n_relu, "get": get, "M_test": m,
-                       "parallelism": ("single GPU" if world == 1 else
-                                       ("row-block kernel shard x%d + one in-place all-gather, %s, replicated alpha solve, test rows sharded"
-                                        % (world, "block-cyclic Cholesky (broadcast per block column)" if dist_chol else "replicated Cholesky")) if shard else
-                                       "fit replicated on %d GPUs (no data-path collective), test rows sharded" % world),
-                       "precision": "float64 kernel build + CG residual; float32 Cholesky (preconditioner) whose trailing updates run "
-                                    "as split-float16 MFMA products (hi+lo, 3 per term, float32 accumulate); float64 means; variances: "
-                                    "float32-grade solves on the float16 pipe + one float64-GRADE residual product on the int8 pipe "
-                                    "(operands cut into exact 8-bit digit planes, 12 exact plane products, float64 combination; level 1)"},
+        result.update({
             "roofline": None,  # filled in below: the dominant kernel when the library timed it, else the stage
             # Cholesky stage = the dominant cost.  `achieved` = algorithmic F_C / stage time.  Its matrix work runs on the
             # float16 pipe at 3 products per float32-grade term, so the hardware peak for it is PEAK_F16 / 3; the
@@ -587,7 +636,7 @@ def main():
                            + ("; stages are the slowest rank's" if world > 1 else ""),
             "fit_info": {"cg_iters": info["refine_iters"], "rel_residual": info["rel_residual"],
                          "clamped_pivots": info["clamped_pivots"], "reg": info["reg"], "alpha_l2": alpha_l2},
-        }
+        })
         if ktimer["on"] and ktimer["launches"] > 0 and ktimer["ms"] > 0.0:
             # `roofline` = the DOMINANT KERNEL, measured live: HIP events around every k_gemm_nt_h3<lower> launch, on the stream
             # it is launched on (nngp_model_update_timer), summed over the timed steps.  achieved = algorithmic flops of the
@@ -659,8 +708,6 @@ def main():
             }
         if shard_report is not None:
             result["shard"] = shard_report
-        elif world > 1:
-            result["shard"] = {"ranks_seen": ranks_seen, "note": "replicate layout: no data-path collective"}
         if world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(n, d, m, n_relu, ms)
         print(json.dumps(result), flush=True)

@@ -342,7 +342,7 @@ def test_bench_launches_its_own_ranks(tmp_path):
     N = 1 record -- starts its ranks as a child torch.distributed.run, relays one parsable line and exits 0.  Two ranks share the
     test box's one GPU (gloo); the line must say two ranks took part and carry the alpha of the one-rank run."""
     import json
-    argv = ["--config", "cfg1", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"]
+    argv = ["--config", "cfg1", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline"]  # --full: fit_info and the shard report
     two = _bench_line(["--gpus", "2"] + argv, {"NNGP_DIST_BACKEND": "gloo"})
     one = _bench_line(["--gpus", "1"] + argv, {})
     assert two["n_gpus"] == 2 and two["shard"]["ranks_seen"] == 2 and one["n_gpus"] == 1
