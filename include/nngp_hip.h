@@ -374,6 +374,9 @@ int nngp_trsm_ticket_queues(int32_t row_tiles, int32_t block_cols, int32_t tail_
 int nngp_trsm_rlt_f32(float* b, int64_t ldb, int64_t m, const float* l, int64_t ldl, const float* dinv,
                       int64_t n, void* stream);
 
+/* The float64 RBF Gaussian process (--kernel_type gp) and the float64 Cholesky operator are declared in
+ * include/nngp_rbf_gp.h: they exist in this library only, with no host build of the same ABI behind them. */
+
 #ifdef __cplusplus
 }
 #endif

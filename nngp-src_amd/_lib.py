@@ -34,6 +34,12 @@ ABI_SYMBOLS = (
     "nngp_trsm_ticket_order", "nngp_trsm_ticket_queues", "nngp_model_reserve", "nngp_alloc_count",
 )
 
+# include/nngp_rbf_gp.h: the float64 RBF GP (--kernel_type gp) and the float64 Cholesky; GPU library only (no host build)
+GP_ABI_SYMBOLS = (
+    "nngp_rbf_gp_create", "nngp_rbf_gp_destroy", "nngp_rbf_gp_set_train", "nngp_rbf_gp_evaluate", "nngp_rbf_gp_terms",
+    "nngp_rbf_gp_predict", "nngp_rbf_gp_kernel", "nngp_rbf_gp_factor_buffer", "nngp_potrf_f64",
+)
+
 
 class NngpArch(ctypes.Structure):
     _fields_ = [("n_dense", ctypes.c_int32), ("reserved", ctypes.c_int32),
@@ -73,6 +79,7 @@ def load(knobs: bool = False):
     import torch  # noqa: F401
     lib = ctypes.CDLL(path)
     bind_prototypes(lib, knobs)
+    bind_gp_prototypes(lib)
     _libs[knobs] = lib
     return lib
 
@@ -155,6 +162,23 @@ def bind_prototypes(lib, knobs: bool = False):
         if name not in ("nngp_last_error", "nngp_model_factor_shift", "nngp_comm_library", "nngp_alloc_count"):
             getattr(lib, name).restype = ctypes.c_int
     lib.nngp_alloc_count.restype = ctypes.c_int64
+    return lib
+
+
+def bind_gp_prototypes(lib):
+    """Argument and result types of include/nngp_rbf_gp.h (the HIP library only)."""
+    vp, i64, i32, dbl = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_double
+    lib.nngp_rbf_gp_create.argtypes = [ctypes.POINTER(vp), i64, i64, i32]
+    lib.nngp_rbf_gp_destroy.argtypes = [vp]
+    lib.nngp_rbf_gp_set_train.argtypes = [vp, vp, vp, i64, i32, vp]
+    lib.nngp_rbf_gp_evaluate.argtypes = [vp, ctypes.POINTER(dbl), ctypes.POINTER(dbl), ctypes.POINTER(dbl), vp]
+    lib.nngp_rbf_gp_terms.argtypes = [vp, ctypes.POINTER(dbl)]
+    lib.nngp_rbf_gp_predict.argtypes = [vp, vp, i64, i32, vp, vp, vp]
+    lib.nngp_rbf_gp_kernel.argtypes = [vp, i64, vp, i64, i32, dbl, vp, i64, vp]
+    lib.nngp_rbf_gp_factor_buffer.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(i64), ctypes.POINTER(i64)]
+    lib.nngp_potrf_f64.argtypes = [vp, i64, i64, vp]
+    for name in GP_ABI_SYMBOLS:
+        getattr(lib, name).restype = ctypes.c_int
     return lib
 
 

@@ -20,6 +20,20 @@ int nngp_potrf_f32(float* a, int64_t n, int64_t ld, float* dinv, int32_t* clampe
     return potrf_f32(a, n, ld, dinv, clamped, 0.0f, (hipStream_t)stream);
 }
 
+int nngp_potrf_f64(double* a, int64_t n, int64_t ld, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    NNGP_REQUIRE(a != nullptr && n > 0 && n % TB == 0, "potrf_f64: n must be a positive multiple of %d (n=%lld)", TB, (long long)n);
+    double* dinv = nullptr;
+    int* status = nullptr;
+    NNGP_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&dinv), sizeof(double) * (size_t)n * TB, s));
+    NNGP_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&status), sizeof(int), s));
+    int rc = potrf_f64(a, n, ld, dinv, status, s);
+    if (rc == 0) rc = potrf_f64_status(status, s, "potrf_f64");
+    (void)hipFreeAsync(dinv, s);
+    (void)hipFreeAsync(status, s);
+    return rc;
+}
+
 int nngp_gemm_nt_f32(float* c, int64_t ldc, const float* a, int64_t lda, const float* b, int64_t ldb, int64_t m,
                      int64_t n, int64_t k, float alpha, float beta, int32_t lower_only, void* stream) {
     NNGP_REQUIRE(a != nullptr && b != nullptr && c != nullptr, "gemm_nt_f32: NULL argument");

@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include "../../include/nngp_hip.h"
+#include "../../include/nngp_rbf_gp.h"
 
 namespace nngp {
 
@@ -147,6 +148,9 @@ int launch_gemm_nt_h3x(float* c, int64_t ldc, const char* a, const char* b, int6
 // ---- potrf.hip ----
 int launch_potrf_leaf(float* a, int64_t ld, float* dinv_block, int32_t* clamped, float pivot_floor, hipStream_t s);
 int potrf_f32(float* a, int64_t n, int64_t ld, float* dinv, int32_t* clamped, float pivot_floor, hipStream_t s);
+// ---- rbf_gp.hip: float64 blocked Cholesky (n multiple of 128; dinv: n x 128; status: device int, -1 or the failed column) ----
+int potrf_f64(double* a, int64_t n, int64_t ld, double* dinv, int* status, hipStream_t s);
+int potrf_f64_status(const int* status, hipStream_t s, const char* who);  // syncs; rc < 0 naming the column if a pivot failed
 int trsm_rlt_f32(float* b, int64_t ldb, int64_t m, const float* l, int64_t ldl, const float* dinv, int64_t n,
                  hipStream_t s);
 

@@ -3,7 +3,7 @@
 
 Prints the same lines as the reference (number of query, shapes, "Kernel construction in ... seconds.",
 "Mean Square Error: ...", "Inference time=... seconds", then the q-error profile) with the GP running on
-the MI355X through libnngp_hip.so.
+the MI355X through libnngp_hip.so.  ``--kernel_type gp`` runs the reference's float64 RBF GP instead (gp.py).
 """
 from __future__ import annotations
 
@@ -91,15 +91,17 @@ def main(args):
         X_test, Y_test, qi_test = X_test[:args.max_num_test], Y_test[:args.max_num_test], qi_test[:args.max_num_test]
     print(X_train.shape, X_test.shape)
     print(Y_train.shape, Y_test.shape)
-    if args.kernel_type == 'gp':
-        raise NotImplementedError("--kernel_type gp is broken in the reference (train.py:114 uses an undefined jit)")
+    if args.kernel_type == 'gp':  # reference train.py:243-244 (its GP_train_and_test, train.py:60-150)
+        from .gp import GP_train_and_test
+        return GP_train_and_test(X_train, Y_train, X_test, Y_test, qi_train, qi_test,
+                                 cov="full" if getattr(args, "full_cov", False) else "diag", pred_stat=pred_stat)
     return NNGP_train_and_test(args, X_train, Y_train, X_test, Y_test, qi_train, qi_test)
 
 
 def make_parser():
     parser = ArgumentParser("NNGP/NTK estimator", formatter_class=ArgumentDefaultsHelpFormatter, conflict_handler="resolve")
     parser.add_argument("--chunk_size", default=64, type=int, help="dimension of factorized encoding")
-    parser.add_argument("--kernel_type", type=str, default='nngp', help='nngp, ntk')
+    parser.add_argument("--kernel_type", type=str, default='nngp', help='nngp, ntk, gp')
     parser.add_argument("--feat_encode", type=str, default='dnn-encoder', help='dnn-encoder,one-hot')
     parser.add_argument('--no-cuda', action='store_true', default=True, help='kept for flag parity; ignored')
     parser.add_argument("--relations", type=str, default='forest')
