@@ -41,9 +41,19 @@ GP_ABI_SYMBOLS = (
 )
 
 
+# include/nngp_activations.h: networks with other activations than ReLU; GPU library only (no host build)
+ACT_ABI_SYMBOLS = ("nngp_kernel_build_act", "nngp_kernel_diag_act", "nngp_model_create_act")
+ACT_RELU, ACT_ABRELU, ACT_ERF = 0, 1, 2
+
+
 class NngpArch(ctypes.Structure):
     _fields_ = [("n_dense", ctypes.c_int32), ("reserved", ctypes.c_int32),
                 ("w_std", ctypes.c_double * MAX_DENSE), ("b_std", ctypes.c_double * MAX_DENSE)]
+
+
+class NngpArchAct(ctypes.Structure):
+    _fields_ = [("base", NngpArch), ("act", ctypes.c_int32 * (MAX_DENSE - 1)),
+                ("p", (ctypes.c_double * 3) * (MAX_DENSE - 1))]
 
 
 class NngpFitInfo(ctypes.Structure):
@@ -80,6 +90,7 @@ def load(knobs: bool = False):
     lib = ctypes.CDLL(path)
     bind_prototypes(lib, knobs)
     bind_gp_prototypes(lib)
+    bind_act_prototypes(lib)
     _libs[knobs] = lib
     return lib
 
@@ -182,6 +193,18 @@ def bind_gp_prototypes(lib):
     return lib
 
 
+def bind_act_prototypes(lib):
+    """Argument and result types of include/nngp_activations.h (the HIP library only)."""
+    vp, i64, i32, dbl = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_double
+    archp = ctypes.POINTER(NngpArchAct)
+    lib.nngp_kernel_build_act.argtypes = [vp, i64, vp, i64, i32, archp, i32, vp, vp, i64, i64, i64, vp]
+    lib.nngp_kernel_diag_act.argtypes = [vp, i64, i32, archp, vp, vp, vp]
+    lib.nngp_model_create_act.argtypes = [ctypes.POINTER(vp), i64, i64, i32, i32, archp, i32, dbl, i32]
+    for name in ACT_ABI_SYMBOLS:
+        getattr(lib, name).restype = ctypes.c_int
+    return lib
+
+
 def check(rc: int, lib=None):
     if rc != 0:
         msg = (lib or load()).nngp_last_error()
@@ -198,6 +221,41 @@ def make_arch(w_std, b_std) -> NngpArch:
     for i, (w, b) in enumerate(zip(w_std, b_std)):
         arch.w_std[i] = w
         arch.b_std[i] = b
+    return arch
+
+
+def canonical_activation(spec):
+    """One hidden layer's activation as ("relu",), ("abrelu", a, b) or ("erf", a, b, c).  ABRelu(0, 1) is ReLU and becomes
+    ("relu",), so that it takes the ReLU kernels and gives their bits."""
+    kind = spec[0]
+    if kind == "relu":
+        return ("relu",)
+    if kind == "abrelu" and len(spec) == 3:
+        a, b = float(spec[1]), float(spec[2])
+        return ("relu",) if (a == 0.0 and b == 1.0) else ("abrelu", a, b)
+    if kind == "erf" and len(spec) == 4:
+        return ("erf", float(spec[1]), float(spec[2]), float(spec[3]))
+    raise ValueError("unknown activation %r" % (spec,))
+
+
+def all_relu(activations) -> bool:
+    return activations is None or all(canonical_activation(a) == ("relu",) for a in activations)
+
+
+def make_arch_act(w_std, b_std, activations) -> NngpArchAct:
+    """nngp_arch_act of Dense layers (w_std, b_std) with activations[l] after Dense layer l (len(w_std) - 1 of them)."""
+    arch = NngpArchAct()
+    arch.base = make_arch(w_std, b_std)
+    activations = list(activations)
+    if len(activations) != arch.base.n_dense - 1:
+        raise ValueError("%d Dense layers need %d activations, got %d" % (arch.base.n_dense, arch.base.n_dense - 1,
+                                                                          len(activations)))
+    codes = {"relu": ACT_RELU, "abrelu": ACT_ABRELU, "erf": ACT_ERF}
+    for l, spec in enumerate(activations):
+        spec = canonical_activation(spec)
+        arch.act[l] = codes[spec[0]]
+        for e, v in enumerate(spec[1:]):
+            arch.p[l][e] = v
     return arch
 
 

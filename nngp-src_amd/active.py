@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import _lib
 from .model import GPModel
 from .util import PredictionStatistics
 
@@ -39,12 +40,14 @@ class ActiveLearner(object):
         X_train = np.ascontiguousarray(X_train, dtype=np.float64)
         Y_train = np.ascontiguousarray(Y_train, dtype=np.float64).reshape(X_train.shape[0], -1)
         n, d = X_train.shape
-        if self._model is None or self._model.n_cap < n or self._model.d != d or self._model.get != self.kernel_type:
+        acts = getattr(kernel_fn, "activations", None)
+        if (self._model is None or self._model.n_cap < n or self._model.d != d or self._model.get != self.kernel_type
+                or self._model.activations != tuple(_lib.canonical_activation(a) for a in (acts or [("relu",)] * len(kernel_fn.w_std[1:])))):
             if self._model is not None:
                 self._model.close()
             self._fitted = None
             self._model = GPModel(max(n, n_cap or n), d, kernel_fn.w_std, kernel_fn.b_std, get=self.kernel_type,
-                                  diag_reg=1e-3, ny=Y_train.shape[1])
+                                  diag_reg=1e-3, ny=Y_train.shape[1], activations=acts)
         # When the new training set extends the fitted one (the loop below appends the selected pool queries), only the
         # new kernel rows are built and the factor is extended (GPModel.append) instead of a full refit.
         prev = self._fitted

@@ -20,7 +20,7 @@ import numpy as np
 
 from . import schemas
 from .active import ActiveLearner
-from .train import build_kernel_fn, load_training_data
+from .train import ACTIVATIONS, kernel_fn_from_args, load_training_data
 from .util import train_test_val_split
 
 
@@ -47,7 +47,7 @@ def main(args, data=None):
     Y_val = np.asarray(Y_val) if Y_val is not None else None
     print(X_train.shape, X_test.shape)
     print(Y_train.shape, Y_test.shape)
-    init_fn, apply_fn, kernel_fn = build_kernel_fn(getattr(args, "n_relu", 1))
+    init_fn, apply_fn, kernel_fn = kernel_fn_from_args(args)
     active_learner = ActiveLearner(args)
     active_learner.active_train(kernel_fn, X_train, Y_train, X_test, Y_test, X_val, Y_val, query_infos_val)
     return active_learner
@@ -75,7 +75,9 @@ def make_parser():
     parser.add_argument("--schema_name", type=str, default='tpch', help='yelp, tpcds, tpch')
     # additions
     parser.add_argument("--top_k", action='store_true', help="select the `budget` largest scores instead of the biased draw")
-    parser.add_argument("--n_relu", type=int, default=1, help="hidden ReLU layers (reference: 1)")
+    parser.add_argument("--n_relu", type=int, default=1, help="hidden layers (reference: 1)")
+    parser.add_argument("--activation", type=str, default="relu", choices=ACTIVATIONS, help="activation of every hidden layer")
+    parser.add_argument("--leaky_alpha", type=float, default=0.1, help="negative slope of --activation leaky_relu")
     parser.add_argument("--max_num_train", type=int, default=None)
     return parser
 

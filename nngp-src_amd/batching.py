@@ -28,7 +28,7 @@ def batch(kernel_fn, batch_size: int = 0, device_count: int = -1, store_on_devic
             return type(blocks[0])(*[np.concatenate([b[i] for b in blocks], axis=0) for i in range(len(blocks[0]))])
         return np.concatenate(blocks, axis=0)
 
-    for attr in ("w_std", "b_std", "n_relu"):
+    for attr in ("w_std", "b_std", "n_relu", "activations", "all_relu"):
         setattr(batched_kernel_fn, attr, getattr(kernel_fn, attr))
     batched_kernel_fn.inner = kernel_fn
     return batched_kernel_fn

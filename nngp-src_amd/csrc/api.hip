@@ -28,6 +28,45 @@ int make_arch_dev(const nngp_arch* arch, ArchDev* out) {
     return 0;
 }
 
+// An ABRelu(a, b) with a == 0 and b == 1 is ReLU: it is given to the ReLU kernels, so that it computes the same bits.
+int make_arch_dev_act(const nngp_arch_act* arch, ArchDev* out) {
+    NNGP_REQUIRE(arch != nullptr, "arch is NULL");
+    NNGP_TRY(make_arch_dev(&arch->base, out));
+    constexpr double kPi = 3.14159265358979323846;
+    out->general = 0;
+    for (int l = 0; l < NNGP_MAX_DENSE - 1; ++l) {
+        out->act[l] = NNGP_ACT_RELU;
+        for (int e = 0; e < 4; ++e) out->ap[l][e] = 0.0;
+    }
+    for (int l = 0; l < arch->base.n_dense - 1; ++l) {
+        const int code = arch->act[l];
+        const double* p = arch->p[l];
+        NNGP_REQUIRE(code == NNGP_ACT_RELU || code == NNGP_ACT_ABRELU || code == NNGP_ACT_ERF,
+                     "arch_act: unknown activation code %d in hidden layer %d", code, l);
+        if (code == NNGP_ACT_RELU) continue;
+        const int np = code == NNGP_ACT_ERF ? 3 : 2;
+        for (int e = 0; e < np; ++e)
+            NNGP_REQUIRE(std::isfinite(p[e]), "arch_act: parameter %d of hidden layer %d is not finite", e, l);
+        if (code == NNGP_ACT_ABRELU) {
+            const double a = p[0], b = p[1];
+            if (a == 0.0 && b == 1.0) continue;
+            out->act[l] = NNGP_ACT_ABRELU;
+            out->ap[l][0] = a * b;
+            out->ap[l][1] = (b - a) * (b - a);
+            out->ap[l][2] = 0.5 * (a * a + b * b);
+        } else {
+            const double a = p[0], b = p[1], c = p[2];
+            out->act[l] = NNGP_ACT_ERF;
+            out->ap[l][0] = a * a * (2.0 / kPi);
+            out->ap[l][1] = 2.0 * b * b;
+            out->ap[l][2] = c * c;
+            out->ap[l][3] = out->ap[l][0] * out->ap[l][1];
+        }
+        out->general = 1;
+    }
+    return 0;
+}
+
 std::atomic<long long> g_alloc_count{0};
 void note_alloc() { g_alloc_count.fetch_add(1, std::memory_order_relaxed); }
 
@@ -80,11 +119,9 @@ int nngp_debug_set(int32_t key, int32_t value) {
 
 const char* nngp_last_error(void) { return g_err; }
 
-int nngp_kernel_diag(const double* x, int64_t n, int32_t d, const nngp_arch* arch, double* diag_nngp,
-                     double* diag_ntk, void* stream) {
+static int kernel_diag(const double* x, int64_t n, int32_t d, const ArchDev& ad, double* diag_nngp, double* diag_ntk,
+                       void* stream) {
     hipStream_t s = (hipStream_t)stream;
-    ArchDev ad;
-    NNGP_TRY(make_arch_dev(arch, &ad));
     NNGP_REQUIRE(x != nullptr && n >= 0 && d > 0, "kernel_diag: bad arguments");
     if (n == 0) return 0;
     double* q = nullptr;
@@ -95,12 +132,24 @@ int nngp_kernel_diag(const double* x, int64_t n, int32_t d, const nngp_arch* arc
     return rc;
 }
 
-int nngp_kernel_build(const double* x1, int64_t n1, const double* x2, int64_t n2, int32_t d, const nngp_arch* arch,
-                      int32_t out_dtype, void* out_nngp, void* out_ntk, int64_t ld, int64_t row_begin,
-                      int64_t row_end, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    ArchDev ad;
+int nngp_kernel_diag(const double* x, int64_t n, int32_t d, const nngp_arch* arch, double* diag_nngp,
+                     double* diag_ntk, void* stream) {
+    ArchDev ad{};
     NNGP_TRY(make_arch_dev(arch, &ad));
+    return kernel_diag(x, n, d, ad, diag_nngp, diag_ntk, stream);
+}
+
+int nngp_kernel_diag_act(const double* x, int64_t n, int32_t d, const nngp_arch_act* arch, double* diag_nngp,
+                         double* diag_ntk, void* stream) {
+    ArchDev ad{};
+    NNGP_TRY(make_arch_dev_act(arch, &ad));
+    return kernel_diag(x, n, d, ad, diag_nngp, diag_ntk, stream);
+}
+
+static int kernel_build(const double* x1, int64_t n1, const double* x2, int64_t n2, int32_t d, const ArchDev& ad,
+                        int32_t out_dtype, void* out_nngp, void* out_ntk, int64_t ld, int64_t row_begin,
+                        int64_t row_end, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     const bool sym = (x2 == nullptr);
     if (sym) n2 = n1;
     NNGP_REQUIRE(n1 >= 0 && n2 >= 0 && d > 0, "kernel_build: bad n1/n2/d");
@@ -142,20 +191,52 @@ int nngp_kernel_build(const double* x1, int64_t n1, const double* x2, int64_t n2
     return rc;
 }
 
+int nngp_kernel_build(const double* x1, int64_t n1, const double* x2, int64_t n2, int32_t d, const nngp_arch* arch,
+                      int32_t out_dtype, void* out_nngp, void* out_ntk, int64_t ld, int64_t row_begin,
+                      int64_t row_end, void* stream) {
+    ArchDev ad{};
+    NNGP_TRY(make_arch_dev(arch, &ad));
+    return kernel_build(x1, n1, x2, n2, d, ad, out_dtype, out_nngp, out_ntk, ld, row_begin, row_end, stream);
+}
+
+int nngp_kernel_build_act(const double* x1, int64_t n1, const double* x2, int64_t n2, int32_t d, const nngp_arch_act* arch,
+                          int32_t out_dtype, void* out_nngp, void* out_ntk, int64_t ld, int64_t row_begin,
+                          int64_t row_end, void* stream) {
+    ArchDev ad{};
+    NNGP_TRY(make_arch_dev_act(arch, &ad));
+    return kernel_build(x1, n1, x2, n2, d, ad, out_dtype, out_nngp, out_ntk, ld, row_begin, row_end, stream);
+}
+
+static int model_create(nngp_model** out, int64_t n_cap, int64_t m_cap, int32_t d, int32_t ny, const ArchDev* arch,
+                        int32_t get, double diag_reg, int32_t diag_reg_absolute_scale);
+
 int nngp_model_create(nngp_model** out, int64_t n_cap, int64_t m_cap, int32_t d, int32_t ny, const nngp_arch* arch,
                       int32_t get, double diag_reg, int32_t diag_reg_absolute_scale) {
     NNGP_REQUIRE(out != nullptr, "model_create: out is NULL");
     *out = nullptr;
+    ArchDev ad{};
+    NNGP_TRY(make_arch_dev(arch, &ad));
+    return model_create(out, n_cap, m_cap, d, ny, &ad, get, diag_reg, diag_reg_absolute_scale);
+}
+
+int nngp_model_create_act(nngp_model** out, int64_t n_cap, int64_t m_cap, int32_t d, int32_t ny, const nngp_arch_act* arch,
+                          int32_t get, double diag_reg, int32_t diag_reg_absolute_scale) {
+    NNGP_REQUIRE(out != nullptr, "model_create: out is NULL");
+    *out = nullptr;
+    ArchDev ad{};
+    NNGP_TRY(make_arch_dev_act(arch, &ad));
+    return model_create(out, n_cap, m_cap, d, ny, &ad, get, diag_reg, diag_reg_absolute_scale);
+}
+
+static int model_create(nngp_model** out, int64_t n_cap, int64_t m_cap, int32_t d, int32_t ny, const ArchDev* arch,
+                        int32_t get, double diag_reg, int32_t diag_reg_absolute_scale) {
     NNGP_REQUIRE(n_cap > 0 && d > 0 && ny > 0 && m_cap >= 0, "model_create: bad sizes");
     NNGP_REQUIRE(get == NNGP_GET_NNGP || get == NNGP_GET_NTK, "model_create: get must be NNGP_GET_NNGP or NNGP_GET_NTK");
     NNGP_REQUIRE(diag_reg >= 0.0, "model_create: diag_reg must be >= 0");
     nngp_model* m = new (std::nothrow) nngp_model();
     NNGP_REQUIRE(m != nullptr, "model_create: out of host memory");
-    int rc = make_arch_dev(arch, &m->arch);
-    if (rc != 0) {
-        delete m;
-        return rc;
-    }
+    int rc = 0;
+    m->arch = *arch;
     m->n_cap = n_cap; m->np_cap = round_up(n_cap, TB); m->m_cap = 0;
     m->ld = m->np_cap;
     m->d = d; m->ny = ny; m->get = get; m->diag_reg = diag_reg; m->absolute = diag_reg_absolute_scale;

@@ -8,6 +8,7 @@
 
 #include "../../include/nngp_hip.h"
 #include "../../include/nngp_rbf_gp.h"
+#include "../../include/nngp_activations.h"
 
 namespace nngp {
 
@@ -80,14 +81,21 @@ extern std::atomic<int> g_knobs[16];
 
 static inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
-// Squared layer parameters in kernel-argument form.
+// Squared layer parameters in kernel-argument form.  The first three members are the all-ReLU architecture (the kernel argument
+// of the ReLU instantiations, ArchRelu in kernel_build.hip, has exactly this layout); the rest says which hidden layer applies
+// which activation (include/nngp_activations.h), with the parameters of its closed form precomputed:
+//   ABRelu(a, b): ap = {a b, (b - a)^2, (a^2 + b^2) / 2, 0};   Erf(a, b, c): ap = {2 a^2 / pi, 2 b^2, c^2, 4 a^2 b^2 / pi}
 struct ArchDev {
     int n_dense;
     double w2[NNGP_MAX_DENSE];
     double b2[NNGP_MAX_DENSE];
+    int general;                            // 0: every hidden layer is ReLU (act / ap unused)
+    int act[NNGP_MAX_DENSE - 1];            // NNGP_ACT_* of hidden layer l (after Dense layer l)
+    double ap[NNGP_MAX_DENSE - 1][4];
 };
 
 int make_arch_dev(const nngp_arch* arch, ArchDev* out);
+int make_arch_dev_act(const nngp_arch_act* arch, ArchDev* out);
 
 // ---- kernel_build.hip ----
 struct BuildArgs {

@@ -15,6 +15,7 @@
 #include "trig_tab.h"
 #include <math.h>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 namespace nngp {
@@ -31,6 +32,21 @@ constexpr double kPi = 3.14159265358979323846;
 constexpr int kCompNI = 16, kCompDeg = 10;                       // intervals of [0, pi] and polynomial degree of the composite map
 constexpr int kCompSize = kCompNI * (kCompDeg + 1) + 1;          // + the amplitude A
 
+// Kernel argument of the all-ReLU instantiations: the leading members of ArchDev, nothing else (the general-activation
+// instantiations take the whole ArchDev).
+struct ArchRelu {
+    int n_dense;
+    double w2[NNGP_MAX_DENSE];
+    double b2[NNGP_MAX_DENSE];
+};
+static_assert(offsetof(ArchRelu, w2) == offsetof(ArchDev, w2) && offsetof(ArchRelu, b2) == offsetof(ArchDev, b2) &&
+              sizeof(ArchRelu) == offsetof(ArchDev, general), "ArchRelu is the head of ArchDev");
+static ArchRelu relu_arch(const ArchDev& a) {
+    ArchRelu r;
+    memcpy(&r, &a, sizeof(r));
+    return r;
+}
+
 __global__ __launch_bounds__(256) void k_row_sqnorm(const double* __restrict__ x, int64_t n, int d,
                                                     double* __restrict__ q) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -46,7 +62,7 @@ __global__ __launch_bounds__(256) void k_row_sqnorm(const double* __restrict__ x
     if (lane == 0) q[row] = s / (double)d;
 }
 
-__global__ __launch_bounds__(256) void k_diag_from_q(const double* __restrict__ q, int64_t n, ArchDev arch,
+__global__ __launch_bounds__(256) void k_diag_from_q(const double* __restrict__ q, int64_t n, ArchRelu arch,
                                                      double* __restrict__ dn, double* __restrict__ dt) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -65,7 +81,7 @@ __global__ __launch_bounds__(256) void k_diag_from_q(const double* __restrict__ 
 
 // One matrix element through Dense,(Relu,Dense)*.  exact_diag: element (i, i) of a symmetric build,
 // where q q' - k^2 == 0 exactly (k is replaced by q so rounding of the dot product cannot leak in).
-__device__ __forceinline__ void layer_map(double k, double q1, double q2, const ArchDev& arch, bool exact_diag,
+__device__ __forceinline__ void layer_map(double k, double q1, double q2, const ArchRelu& arch, bool exact_diag,
                                           double& out_k, double& out_t) {
     double t = 0.0;
     if (exact_diag) k = q1;
@@ -95,6 +111,10 @@ __device__ __forceinline__ void layer_map(double k, double q1, double q2, const 
     out_t = t;
 }
 
+// The same for a network with other activations (defined below, after the float64 helpers it uses).
+__device__ __forceinline__ void layer_map_act(double k, double q1, double q2, const ArchDev& arch, bool exact_diag,
+                                              double& out_k, double& out_t);
+
 template <typename T>
 __device__ __forceinline__ void store4(T* base, int64_t ld, int64_t i, int64_t j, int64_t i_end, int64_t j_end,
                                        const double v[4], bool vec_ok) {
@@ -117,8 +137,9 @@ __device__ __forceinline__ void store4(T* base, int64_t ld, int64_t i, int64_t j
 // MFMA = true: the Gram entries x.x' are accumulated on the float64 matrix cores (v_mfma_f64_16x16x4_f64, 2x2 tiles of
 // 16x16 per wave, 4 waves = the 64x64 tile) and handed to the epilogue's 4x4-per-thread layout through LDS;
 // MFMA = false: the same sums on the float64 VALU (the default; the MFMA form is selected by nngp_debug_set(3, 3)).
-template <bool MFMA>
-__global__ __launch_bounds__(256) void k_build(BuildArgs a, ArchDev arch, int64_t tiles_c, int vec_ok) {
+// Arch = ArchDev: a network with other activations than ReLU (layer_map_act).
+template <bool MFMA, typename Arch = ArchRelu>
+__global__ __launch_bounds__(256) void k_build(BuildArgs a, Arch arch, int64_t tiles_c, int vec_ok) {
     __shared__ __attribute__((aligned(16))) double smem[KT * LDP];  // As | Bs during the k-loop, T for the mirror
     constexpr int LDS_ = MFMA ? LDM : LDP;
     double* As = smem;              // [KC][LDS_]
@@ -250,7 +271,10 @@ __global__ __launch_bounds__(256) void k_build(BuildArgs a, ArchDev arch, int64_
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const int64_t gj = j0 + tx * 4 + c;
-            layer_map(acc[r][c] * inv_d, q1v, q2v[c], arch, a.sym && gi == gj, kn[r][c], kt[r][c]);
+            if constexpr (std::is_same<Arch, ArchDev>::value)
+                layer_map_act(acc[r][c] * inv_d, q1v, q2v[c], arch, a.sym && gi == gj, kn[r][c], kt[r][c]);
+            else
+                layer_map(acc[r][c] * inv_d, q1v, q2v[c], arch, a.sym && gi == gj, kn[r][c], kt[r][c]);
         }
     }
     const bool vec = vec_ok != 0;
@@ -349,6 +373,95 @@ __device__ __forceinline__ double pi_minus_atan2(double s, double k, const doubl
     return mx > 0.0 ? pmt : 0.5 * kPi;
 }
 
+// ---- the other activations (include/nngp_activations.h; ap: ArchDev::ap) ----------------------------------------------------
+// act_diag: a diagonal entry q through hidden layer `code` -- q' and kdot.  It is also what a row's q becomes, so the symmetric
+// build's diagonal, the rows' q of its cross entries and k_diag_from_q_act all go through this one function (bit-identical).
+// Erf: asin(u / sqrt(u^2 + w^2)) = atan2(u, w) = pi_minus_atan2(w, u) - pi / 2, with w = sqrt(1 + 4 b^2 q) on the diagonal.
+__device__ __forceinline__ void act_diag(int code, const double* ap, double q, const double* __restrict__ tab, double& qo,
+                                         double& kd) {
+    if (code == NNGP_ACT_ERF) {
+        const double w = fast_sqrt_pos(fma(2.0 * ap[1], q, 1.0));  // >= 1: q >= 0
+        qo = fma(ap[0], pi_minus_atan2(w, ap[1] * q, tab) - 0.5 * kPi, ap[2]);
+        kd = ap[3] * fast_rcp(w);
+    } else if (code == NNGP_ACT_ABRELU) {
+        qo = ap[2] * q;
+        kd = ap[2];
+    } else {
+        qo = 0.5 * q;
+        kd = 0.5;
+    }
+}
+
+// act_cross: an off-diagonal entry k with diagonals q1, q2.  Erf: r = 1 + 2 b^2 (q1 + q2) + 4 b^4 (q1 q2 - k^2) -- r >= 1 and no term
+// cancels, so w keeps its relative precision for near-duplicate rows (the product form (1 + 2 b^2 q1)(1 + 2 b^2 q2) - u^2 loses
+// ~6 digits at raw forest norms, and the arcsine is first-order sensitive to w).  The bracket is fma(q1, q2, -k^2) plus the
+// rounding error of k^2 (Kahan's difference of products, one more fma): without it that rounding alone is q ulp of r.
+// ABRelu(a, b) = a b k + (b - a)^2 relu(k): the ReLU map's own arithmetic, then one fma.
+__device__ __forceinline__ void act_cross(int code, const double* ap, double k, double q1, double q2,
+                                          const double* __restrict__ tab, double& ko, double& kd) {
+    if (code == NNGP_ACT_ERF) {
+        const double kk = k * k;
+        const double br = fmax(fma(q1, q2, -kk) + fma(-k, k, kk), 0.0);
+        const double w = fast_sqrt_pos(fma(ap[1] * ap[1], br, fma(ap[1], q1 + q2, 1.0)));
+        ko = fma(ap[0], pi_minus_atan2(w, ap[1] * k, tab) - 0.5 * kPi, ap[2]);
+        kd = ap[3] * fast_rcp(w);
+    } else {
+        const double rr = fma(q1, q2, -k * k);
+        const double s = rr > 0.0 ? fast_sqrt_pos(rr > 0.0 ? rr : 1.0) : 0.0;
+        const double kr = pi_minus_atan2(s, k, tab) * (0.5 / kPi);
+        const double kk = fma(kr, k, s * (0.5 / kPi));
+        if (code == NNGP_ACT_ABRELU) {
+            ko = fma(ap[0], k, ap[1] * kk);
+            kd = fma(ap[1], kr, ap[0]);
+        } else {
+            ko = kk;
+            kd = kr;
+        }
+    }
+}
+
+__device__ __forceinline__ void layer_map_act(double k, double q1, double q2, const ArchDev& arch, bool exact_diag,
+                                              double& out_k, double& out_t) {
+    const double* tab = &kTrigTab[0][0];
+    double t = 0.0;
+    if (exact_diag) k = q1;
+    for (int l = 0; l < arch.n_dense; ++l) {
+        const double w2 = arch.w2[l], b2 = arch.b2[l];
+        k = fma(w2, k, b2);
+        q1 = fma(w2, q1, b2);
+        q2 = fma(w2, q2, b2);
+        t = fma(w2, t, k);
+        if (l < arch.n_dense - 1) {
+            double kd, unused;
+            if (exact_diag) act_diag(arch.act[l], arch.ap[l], k, tab, k, kd);
+            else act_cross(arch.act[l], arch.ap[l], k, q1, q2, tab, k, kd);
+            t *= kd;
+            act_diag(arch.act[l], arch.ap[l], q1, tab, q1, unused);
+            act_diag(arch.act[l], arch.ap[l], q2, tab, q2, unused);
+        }
+    }
+    out_k = k;
+    out_t = t;
+}
+
+__global__ __launch_bounds__(256) void k_diag_from_q_act(const double* __restrict__ q, int64_t n, ArchDev arch,
+                                                         double* __restrict__ dn, double* __restrict__ dt) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double k = q[i], t = 0.0;
+    for (int l = 0; l < arch.n_dense; ++l) {
+        k = fma(arch.w2[l], k, arch.b2[l]);
+        t = fma(arch.w2[l], t, k);
+        if (l < arch.n_dense - 1) {
+            double kd;
+            act_diag(arch.act[l], arch.ap[l], k, &kTrigTab[0][0], k, kd);
+            t *= kd;
+        }
+    }
+    if (dn) dn[i] = k;
+    if (dt) dt[i] = t;
+}
+
 // K1, second form.  One 64 x 64 output tile per 256-thread workgroup (4 waves, 32 x 32 outputs each), MANY workgroups per CU:
 //   * Gram entries on the float64 matrix cores (v_mfma_f64_16x16x4_f64, 2 x 2 blocks per wave).  The x1 / x2 row panels are
 //     staged through LDS in k-chunks of 16, ROW-major with a 2-double pad (stores run along k without bank conflicts, and a
@@ -374,14 +487,17 @@ constexpr int TLD = 34;       // row stride of the per-wave 16 x 32 output buffe
 // COMP (round 4): NNGP outputs only, no biases, >= 2 ReLU layers -- the whole layer recursion is then sqrt(q q') A G(pi - theta0) with ONE
 // univariate function G of the first layer's angle (comp_table below): one sqrt + one arctangent + a degree-10 polynomial per entry
 // instead of a sqrt and an arctangent per layer.  a.comp: [kCompNI][kCompDeg + 1] coefficients + A, staged in LDS.
-template <int MKC, bool PREFETCH, int MINWG, bool LDSOUT, bool COMP>
-__global__ __launch_bounds__(256, MINWG) void k_build_mfma(BuildArgs a, ArchDev arch, int64_t tiles_r, int64_t tiles_c,
+// GEN: the other activations (arch is the whole ArchDev; act_cross / act_diag per hidden layer).  The rows' and columns' q after
+// each Dense layer are computed once per tile into LDS (qs) instead of once per entry.
+template <int MKC, bool PREFETCH, int MINWG, bool LDSOUT, bool COMP, bool GEN = false>
+__global__ __launch_bounds__(256, MINWG) void k_build_mfma(BuildArgs a, std::conditional_t<GEN, ArchDev, ArchRelu> arch, int64_t tiles_r, int64_t tiles_c,
                                                            int64_t sup_r, int64_t sup_c, int vec_ok, int ablate) {
     constexpr int MLD = MKC + 2;  // LDS row stride (doubles): rows 16-byte aligned, quarter-waves on distinct banks
     constexpr int NLD = MKC * 64 / 256;  // doubles per thread and operand per chunk
     __shared__ __attribute__((aligned(16))) double smem[2 * KT * MLD];  // As | Bs in the k-loop, 4 output buffers afterwards
     __shared__ __attribute__((aligned(16))) double tab[65 * 4];
     __shared__ double ctab[COMP ? kCompSize : 1];
+    __shared__ double qs[GEN ? (NNGP_MAX_DENSE - 1) * 2 * KT : 1];  // [layer][64 rows | 64 columns], before the activation
     static_assert(4 * 16 * TLD <= 2 * KT * MLD, "the output buffers alias the panel buffers");
     double* As = smem;             // [KT][MLD]
     double* Bs = smem + KT * MLD;  // [KT][MLD]
@@ -410,6 +526,18 @@ __global__ __launch_bounds__(256, MINWG) void k_build_mfma(BuildArgs a, ArchDev 
     for (int i = tid; i < 65 * 4; i += 256) tab[i] = kTrigTab[i >> 2][i & 3];
     if (COMP)
         for (int i = tid; i < kCompSize; i += 256) ctab[i] = a.comp[i];
+    if constexpr (GEN) {  // read after the k-loop's first barrier
+        if (tid < 2 * KT) {
+            const int64_t g = tid < KT ? i0 + tid : j0 + tid - KT;
+            double q = tid < KT ? (g < i_end ? a.q1[g] : 0.0) : (g < j_end ? a.q2[g] : 0.0);
+            for (int l = 0; l < arch.n_dense - 1; ++l) {
+                double unused;
+                q = fma(arch.w2[l], q, arch.b2[l]);
+                qs[l * 2 * KT + tid] = q;
+                act_diag(arch.act[l], arch.ap[l], q, &kTrigTab[0][0], q, unused);
+            }
+        }
+    }
 
     const int lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1, l16 = lane & 15, lg = lane >> 4;
@@ -526,6 +654,27 @@ __global__ __launch_bounds__(256, MINWG) void k_build_mfma(BuildArgs a, ArchDev 
                         k = rho * (amp * p);
                     }
                     kv[j][r] = k;
+                }
+            } else if constexpr (GEN) {
+                for (int l = 0; l < arch.n_dense; ++l) {
+                    const double w2 = arch.w2[l], b2 = arch.b2[l];
+                    const bool hidden = l < arch.n_dense - 1;
+                    const int code = hidden ? arch.act[l] : NNGP_ACT_RELU;
+                    const double* ap = arch.ap[hidden ? l : 0];
+                    const double q2l = hidden ? qs[l * 2 * KT + KT + wn * 32 + j * 16 + l16] : 0.0;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        double k = fma(w2, kv[j][r], b2);
+                        double t = fma(w2, tv[j][r], k);
+                        if (hidden) {
+                            double kd;
+                            if (dg[r]) act_diag(code, ap, k, tab, k, kd);  // theta = 0 exactly, as in k_diag_from_q_act
+                            else act_cross(code, ap, k, qs[l * 2 * KT + wm * 32 + i * 16 + lg + 4 * r], q2l, tab, k, kd);
+                            t *= kd;
+                        }
+                        kv[j][r] = k;
+                        tv[j][r] = t;
+                    }
                 }
             } else
             for (int l = 0; l < arch.n_dense; ++l) {
@@ -655,7 +804,10 @@ int launch_row_sqnorm(const double* x, int64_t n, int d, double* q, hipStream_t 
 
 int launch_diag_from_q(const double* q, int64_t n, const ArchDev& arch, double* dn, double* dt, hipStream_t s) {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(k_diag_from_q, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, q, n, arch, dn, dt);
+    if (arch.general)
+        hipLaunchKernelGGL(k_diag_from_q_act, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, q, n, arch, dn, dt);
+    else
+        hipLaunchKernelGGL(k_diag_from_q, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, q, n, relu_arch(arch), dn, dt);
     NNGP_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -740,9 +892,9 @@ static bool comp_build_host(const ArchDev& arch, double* out) {
 }
 
 // the table of this architecture on the device (built once per process and architecture), or NULL when the composite form does
-// not apply: biases, fewer than two ReLU layers, a table that failed its check
+// not apply: biases, fewer than two ReLU layers, another activation than ReLU, a table that failed its check
 static const double* comp_table(const ArchDev& arch) {
-    if (arch.n_dense < 3) return nullptr;
+    if (arch.n_dense < 3 || arch.general) return nullptr;
     for (int l = 0; l < arch.n_dense; ++l)
         if (arch.b2[l] != 0.0 || !(arch.w2[l] > 0.0)) return nullptr;
     int device = 0;
@@ -768,10 +920,11 @@ static const double* comp_table(const ArchDev& arch) {
     return dev;
 }
 
-int launch_kernel_build(const BuildArgs& a_in, const ArchDev& arch, hipStream_t s) {
+int launch_kernel_build(const BuildArgs& a_in, const ArchDev& arch_in, hipStream_t s) {
+    const ArchRelu arch = relu_arch(arch_in);  // the ReLU instantiations' argument (arch_in.general == 0)
     BuildArgs a = a_in;
     // NNGP outputs only, no biases, >= 2 ReLU layers: the composite map (debug key 5 = 63: the per-layer recursion)
-    a.comp = (a.ntk64 == nullptr && a.ntk32 == nullptr && !a.no_comp && NNGP_KNOB(5) != 63) ? comp_table(arch) : nullptr;
+    a.comp = (a.ntk64 == nullptr && a.ntk32 == nullptr && !a.no_comp && NNGP_KNOB(5) != 63) ? comp_table(arch_in) : nullptr;
     const int64_t rows = a.row_end - a.row_begin;
     if (rows <= 0 || a.n2 <= 0) return 0;
     NNGP_REQUIRE(a.d > 0, "kernel_build: d must be positive");
@@ -796,7 +949,18 @@ int launch_kernel_build(const BuildArgs& a_in, const ArchDev& arch, hipStream_t 
     // re-tiled the accumulators through LDS and staged the panels k-major (8-way bank conflicts on the stores).  k_build_mfma
     // keeps the epilogue in the accumulator layout, overlaps MFMA and VALU across co-resident workgroups and evaluates the
     // map with the fast float64 helpers.  Debug key 3 = 4: the round-1 kernel, for A/B timing.
-    if (NNGP_KNOB(3) == 4 || NNGP_KNOB(3) == 3) {
+    if (arch_in.general) {  // other activations: one instantiation of each form, the MFMA one by default
+        if (NNGP_KNOB(3) == 4)
+            hipLaunchKernelGGL((k_build<false, ArchDev>), dim3((unsigned)nblocks), dim3(256), 0, s, a, arch_in, tiles_c, vec_ok);
+        else {
+            const int64_t sup_r = (tiles_r + 7) / 8, sup_c = (tiles_c + 7) / 8;
+            const int64_t nsup = a.sym ? sup_r * (sup_r + 1) / 2 : sup_r * sup_c;
+            const int64_t grid = ((nsup + 7) / 8) * 8 * 64;
+            NNGP_REQUIRE(grid < (int64_t)2147483647, "kernel_build: grid too large (%lld workgroups)", (long long)grid);
+            hipLaunchKernelGGL((k_build_mfma<16, true, 3, false, false, true>), dim3((unsigned)grid), dim3(256), 0, s, a, arch_in,
+                               tiles_r, tiles_c, sup_r, sup_c, vec_ok, 0);
+        }
+    } else if (NNGP_KNOB(3) == 4 || NNGP_KNOB(3) == 3) {
         if (NNGP_KNOB(3) == 3)
             hipLaunchKernelGGL(k_build<true>, dim3((unsigned)nblocks), dim3(256), 0, s, a, arch, tiles_c, vec_ok);
         else

@@ -20,17 +20,29 @@ _COV = {False: _lib.COV_NONE, None: _lib.COV_NONE, "none": _lib.COV_NONE, "diag"
 
 class GPModel:
     def __init__(self, n_cap: int, d: int, w_std, b_std, get: str = "nngp", diag_reg: float = 1e-3,
-                 diag_reg_absolute_scale: bool = False, ny: int = 1, m_cap: int = 0, knobs: bool = False):
+                 diag_reg_absolute_scale: bool = False, ny: int = 1, m_cap: int = 0, knobs: bool = False,
+                 activations=None):
+        """activations: one per hidden layer, as ``stax.KernelFn.activations`` (None: all ReLU).  An all-ReLU model is
+        created through nngp_model_create, any other through nngp_model_create_act."""
         if get not in _GET:
             raise ValueError("get must be 'nngp' or 'ntk', got %r" % (get,))
         self.lib = _lib.load(knobs)  # knobs=True: the timing-knob build (A/B tests and scripts/ only)
         self.device = _lib.require_gpu()
         self.get, self.d, self.ny, self.n_cap = get, int(d), int(ny), int(n_cap)
         self.arch = _lib.make_arch(w_std, b_std)
+        n_hidden = self.arch.n_dense - 1
+        self.activations = tuple(_lib.canonical_activation(a) for a in (activations or [("relu",)] * n_hidden))
+        self.all_relu = _lib.all_relu(self.activations)
         self.handle = ctypes.c_void_p()
-        self._check(self.lib.nngp_model_create(ctypes.byref(self.handle), int(n_cap), int(m_cap), int(d), int(ny),
-                                              ctypes.byref(self.arch), _GET[get], float(diag_reg),
-                                              int(bool(diag_reg_absolute_scale))))
+        if self.all_relu:
+            self._check(self.lib.nngp_model_create(ctypes.byref(self.handle), int(n_cap), int(m_cap), int(d), int(ny),
+                                                  ctypes.byref(self.arch), _GET[get], float(diag_reg),
+                                                  int(bool(diag_reg_absolute_scale))))
+        else:
+            arch_act = _lib.make_arch_act(w_std, b_std, self.activations)
+            self._check(self.lib.nngp_model_create_act(ctypes.byref(self.handle), int(n_cap), int(m_cap), int(d), int(ny),
+                                                      ctypes.byref(arch_act), _GET[get], float(diag_reg),
+                                                      int(bool(diag_reg_absolute_scale))))
         if m_cap > 0:  # predict-side workspace now, not inside the first predict (SURVEY 8b ownership rule)
             self._check(self.lib.nngp_model_reserve(self.handle, int(m_cap), _lib.COV_DIAG))
         self.n = 0
@@ -199,20 +211,38 @@ class GPModel:
         w = np.array([self.arch.w_std[i] for i in range(self.arch.n_dense)])
         b = np.array([self.arch.b_std[i] for i in range(self.arch.n_dense)])
         info = self.info()
-        np.savez(path, format=np.array("nngp-src_amd GPModel v1"), x=x, y=y, w_std=w, b_std=b, get=np.array(self.get),
+        extra = {}
+        if not self.all_relu:  # v2: the activations as (code, a, b, c) rows; a ReLU model keeps writing v1
+            codes = {"relu": _lib.ACT_RELU, "abrelu": _lib.ACT_ABRELU, "erf": _lib.ACT_ERF}
+            extra["activations"] = np.array([[codes[a[0]]] + list(a[1:]) + [0.0] * (4 - len(a)) for a in self.activations],
+                                            dtype=np.float64).reshape(-1, 4)
+        np.savez(path, format=np.array("nngp-src_amd GPModel v1" if self.all_relu else "nngp-src_amd GPModel v2"), x=x, y=y,
+                 w_std=w, b_std=b, get=np.array(self.get),
                  diag_reg=np.array(self._diag_reg), absolute=np.array(self._absolute), n_cap=np.array(self.n_cap),
-                 alpha=self.alpha().cpu().numpy(), reg=np.array(info["reg"]))
+                 alpha=self.alpha().cpu().numpy(), reg=np.array(info["reg"]), **extra)
         torch.cuda.synchronize()
 
     @classmethod
     def load(cls, path: str, m_cap: int = 0, check: bool = True):
         """Rebuild a saved model on the current device; ``check``: alpha must agree with the saved one to 1e-8."""
         z = np.load(path if str(path).endswith(".npz") else str(path) + ".npz", allow_pickle=False)
-        if str(z["format"]) != "nngp-src_amd GPModel v1":
+        fmt = str(z["format"])
+        if fmt not in ("nngp-src_amd GPModel v1", "nngp-src_amd GPModel v2"):
             raise _lib.NngpError("load: %s is not a GPModel checkpoint" % path)
+        acts = None
+        if fmt.endswith("v2"):
+            names = {_lib.ACT_RELU: "relu", _lib.ACT_ABRELU: "abrelu", _lib.ACT_ERF: "erf"}
+            nparams = {"relu": 0, "abrelu": 2, "erf": 3}
+            acts = []
+            for row in z["activations"]:
+                if int(row[0]) not in names:
+                    raise _lib.NngpError("load: %s: unknown activation code %r" % (path, row[0]))
+                kind = names[int(row[0])]
+                acts.append((kind,) + tuple(float(v) for v in row[1:1 + nparams[kind]]))
         x, y = z["x"], z["y"]
         model = cls(max(int(z["n_cap"]), x.shape[0]), x.shape[1], z["w_std"].tolist(), z["b_std"].tolist(), get=str(z["get"]),
-                    diag_reg=float(z["diag_reg"]), diag_reg_absolute_scale=bool(z["absolute"]), ny=y.shape[1], m_cap=m_cap)
+                    diag_reg=float(z["diag_reg"]), diag_reg_absolute_scale=bool(z["absolute"]), ny=y.shape[1], m_cap=m_cap,
+                    activations=acts)
         model.fit(x, y)
         if check:
             a, a0 = model.alpha().cpu().numpy(), z["alpha"]

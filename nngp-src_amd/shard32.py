@@ -31,10 +31,13 @@ from . import distributed as D
 class HipRowOps:
     """The per-rank arithmetic of the row-sharded layout on one MI355X through the C ABI.  Raises without the library or a GPU."""
 
-    def __init__(self, n: int, d: int, w_std, b_std, diag_reg: float = 1e-3, diag_reg_absolute_scale: bool = False, world: int = 1):
+    def __init__(self, n: int, d: int, w_std, b_std, diag_reg: float = 1e-3, diag_reg_absolute_scale: bool = False, world: int = 1,
+                 activations=None):
         import ctypes
         import torch
         from . import _lib
+        if not _lib.all_relu(activations):  # its row operations take the ReLU architecture only
+            raise NotImplementedError("shard32 supports Dense,(Relu,Dense)* networks only, got activations %r" % (activations,))
         from .model import GPModel
         self._lib, self._ct, self.torch = _lib, ctypes, torch
         self.lib = _lib.load()

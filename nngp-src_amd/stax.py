@@ -4,9 +4,11 @@ train.py:161-164, estimator.py:27-30, active/active_train.py:40-43).
     init_fn, apply_fn, kernel_fn = stax.serial(stax.Dense(512), stax.Relu(), stax.Dense(1))
     k = kernel_fn(x1, x2, 'nngp')          # computed by the HIP kernel build (nngp_kernel_build)
 
-Supported topology: Dense, (Relu, Dense)* -- what the reference builds; widths do not enter the
-infinite-width kernel.  ``init_fn`` / ``apply_fn`` are the finite-width network in NumPy (NTK
-parameterisation), kept for API shape; the reference never calls them.
+Supported topology: Dense, (act, Dense)* with act one of Relu (what the reference builds), Erf, ABRelu,
+LeakyRelu and Abs, chosen per hidden layer; widths do not enter the infinite-width kernel.  An all-ReLU
+network takes the ReLU entry points of include/nngp_hip.h, any other the ``_act`` entry points of
+include/nngp_activations.h.  ``init_fn`` / ``apply_fn`` are the finite-width network in NumPy (NTK
+parameterisation); the reference never calls them, the tests use them as a Monte Carlo pin.
 """
 from __future__ import annotations
 
@@ -19,7 +21,7 @@ import numpy as np
 from . import _lib
 
 Kernel = collections.namedtuple("Kernel", ["nngp", "ntk"])
-_Layer = collections.namedtuple("_Layer", ["kind", "out_dim", "w_std", "b_std"])
+_Layer = collections.namedtuple("_Layer", ["kind", "out_dim", "w_std", "b_std", "act"], defaults=(None,))
 
 
 def Dense(out_dim, W_std=1.0, b_std=None, parameterization="ntk"):
@@ -28,20 +30,63 @@ def Dense(out_dim, W_std=1.0, b_std=None, parameterization="ntk"):
     return _Layer("dense", int(out_dim), float(W_std), 0.0 if b_std is None else float(b_std))
 
 
-def Relu():
-    return _Layer("relu", None, None, None)
+def _act(spec):
+    for v in spec[1:]:
+        if not math.isfinite(v):
+            raise ValueError("activation parameters must be finite, got %r" % (spec,))
+    return _Layer(spec[0], None, None, None, spec)
+
+
+# do_stabilize (neural-tangents' rescaling for numerical range) is accepted and ignored: the float64 closed forms need none.
+def Relu(do_stabilize=False):
+    return _act(("relu",))
+
+
+def ABRelu(a, b, do_stabilize=False):
+    """phi(x) = a x for x < 0, b x for x >= 0."""
+    return _act(("abrelu", float(a), float(b)))
+
+
+def LeakyRelu(alpha, do_stabilize=False):
+    return _act(("abrelu", float(alpha), 1.0))
+
+
+def Abs(do_stabilize=False):
+    return _act(("abrelu", -1.0, 1.0))
+
+
+def Erf(a=1.0, b=1.0, c=0.0):
+    """phi(x) = a erf(b x) + c."""
+    return _act(("erf", float(a), float(b), float(c)))
+
+
+def _phi(spec, h):
+    if spec[0] == "relu":
+        return np.maximum(h, 0.0)
+    if spec[0] == "abrelu":
+        return np.where(h < 0.0, spec[1] * h, spec[2] * h)
+    import torch
+    return spec[1] * torch.special.erf(torch.from_numpy(spec[2] * h)).numpy() + spec[3]
 
 
 class KernelFn:
-    """kernel_fn(x1, x2=None, get=None): closed-form kernel of Dense,(Relu,Dense)* on the GPU."""
+    """kernel_fn(x1, x2=None, get=None): closed-form kernel of Dense,(act,Dense)* on the GPU."""
 
-    def __init__(self, w_std, b_std):
+    def __init__(self, w_std, b_std, activations=None):
         self.w_std = tuple(float(w) for w in w_std)
         self.b_std = tuple(float(b) for b in b_std)
-        self.n_relu = len(self.w_std) - 1
+        self.n_relu = len(self.w_std) - 1  # hidden layers (the name is the all-ReLU one)
+        acts = [("relu",)] * self.n_relu if activations is None else list(activations)
+        if len(acts) != self.n_relu:
+            raise ValueError("%d Dense layers need %d activations" % (len(self.w_std), self.n_relu))
+        # per hidden layer: ("relu",), ("abrelu", a, b) or ("erf", a, b, c); ABRelu(0, 1) is stored as ("relu",)
+        self.activations = tuple(_lib.canonical_activation(a) for a in acts)
+        self.all_relu = _lib.all_relu(self.activations)
 
     def _arch(self):
-        return _lib.make_arch(self.w_std, self.b_std)
+        if self.all_relu:
+            return _lib.make_arch(self.w_std, self.b_std)
+        return _lib.make_arch_act(self.w_std, self.b_std, self.activations)
 
     def __call__(self, x1, x2=None, get=None, *, rows=None, as_numpy=True):
         import torch
@@ -63,7 +108,8 @@ class KernelFn:
         outs = {g: torch.empty((n1, n2), dtype=torch.float64, device=dev) for g in set(gets)}
         if n1 > 0 and n2 > 0 and r1 > r0:
             arch = self._arch()
-            _lib.check(lib.nngp_kernel_build(_lib.ptr(x1d), n1, _lib.ptr(x2d), n2, d, ctypes.byref(arch),
+            build = lib.nngp_kernel_build if self.all_relu else lib.nngp_kernel_build_act
+            _lib.check(build(_lib.ptr(x1d), n1, _lib.ptr(x2d), n2, d, ctypes.byref(arch),
                                              _lib.DTYPE_F64, _lib.ptr(outs.get("nngp")), _lib.ptr(outs.get("ntk")),
                                              n2, r0, r1, _lib.stream_ptr()))
         res = {g: (t[r0:r1] if rows is not None else t) for g, t in outs.items()}
@@ -77,15 +123,17 @@ class KernelFn:
 
 
 def serial(*layers):
-    """Dense,(Relu,Dense)* -> (init_fn, apply_fn, kernel_fn)."""
+    """Dense,(act,Dense)* -> (init_fn, apply_fn, kernel_fn); act: Relu, Erf, ABRelu, LeakyRelu or Abs."""
     if not layers or any(not isinstance(l, _Layer) for l in layers):
-        raise TypeError("serial() takes stax.Dense(...) / stax.Relu() layers")
+        raise TypeError("serial() takes stax.Dense(...) and activation layers (stax.Relu(), stax.Erf(), ...)")
     kinds = [l.kind for l in layers]
-    ok = len(kinds) % 2 == 1 and all(k == ("dense" if i % 2 == 0 else "relu") for i, k in enumerate(kinds))
+    ok = len(kinds) % 2 == 1 and all((k == "dense") == (i % 2 == 0) for i, k in enumerate(kinds))
     if not ok:
-        raise NotImplementedError("supported topology is Dense,(Relu,Dense)* -- got %s" % kinds)
+        raise NotImplementedError("supported topology is Dense,(act,Dense)* with act one of Relu, Erf, ABRelu, "
+                                  "LeakyRelu, Abs -- got %s" % kinds)
     dense = [l for l in layers if l.kind == "dense"]
-    kernel_fn = KernelFn([l.w_std for l in dense], [l.b_std for l in dense])
+    acts = [l.act for l in layers[1::2]]
+    kernel_fn = KernelFn([l.w_std for l in dense], [l.b_std for l in dense], acts)
 
     def init_fn(rng, input_shape):
         gen = rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)
@@ -95,12 +143,16 @@ def serial(*layers):
             fan_in = l.out_dim
         return tuple(input_shape[:-1]) + (fan_in,), params
 
-    def apply_fn(params, x):
+    def apply_fn(params, x, readout=True):
+        """The finite-width network.  readout=False: the last hidden layer's activations instead of the output (the
+        features the last Dense layer reads; their Gram matrix w_std^2 phi phi^T / width + b_std^2 is the finite-width NNGP)."""
         h = np.asarray(x, dtype=np.float64)
         for i, (l, (w, b)) in enumerate(zip(dense, params)):
+            if i == len(dense) - 1 and not readout:
+                break
             h = l.w_std / math.sqrt(h.shape[-1]) * (h @ w) + l.b_std * b
             if i < len(dense) - 1:
-                h = np.maximum(h, 0.0)
+                h = _phi(acts[i], h)
         return h
 
     return init_fn, apply_fn, kernel_fn

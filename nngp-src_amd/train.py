@@ -21,12 +21,32 @@ from .util import PredictionStatistics, train_test_val_split
 pred_stat = PredictionStatistics()
 
 
-def build_kernel_fn(n_relu: int = 1):
+ACTIVATIONS = ("relu", "erf", "abs", "leaky_relu")
+
+
+def activation_layer(name: str = "relu", leaky_alpha: float = 0.1):
+    """The hidden-layer activation --activation names (every hidden layer gets the same one)."""
+    if name == "relu":
+        return stax.Relu()
+    if name == "erf":
+        return stax.Erf()
+    if name == "abs":
+        return stax.Abs()
+    if name == "leaky_relu":
+        return stax.LeakyRelu(leaky_alpha)
+    raise ValueError("unknown activation %r (one of %s)" % (name, ", ".join(ACTIVATIONS)))
+
+
+def build_kernel_fn(n_relu: int = 1, activation: str = "relu", leaky_alpha: float = 0.1):
     layers = [stax.Dense(512)]
     for _ in range(n_relu):
-        layers += [stax.Relu(), stax.Dense(512)]
+        layers += [activation_layer(activation, leaky_alpha), stax.Dense(512)]
     layers[-1] = stax.Dense(1)
     return stax.serial(*layers)
+
+
+def kernel_fn_from_args(args):
+    return build_kernel_fn(getattr(args, "n_relu", 1), getattr(args, "activation", "relu"), getattr(args, "leaky_alpha", 0.1))
 
 
 def NNGP_train_and_test(args, X_train, Y_train, X_test, Y_test, query_infos_train=None, query_infos_test=None):
@@ -34,7 +54,7 @@ def NNGP_train_and_test(args, X_train, Y_train, X_test, Y_test, query_infos_trai
         pred_mean, pred_cov = pred_fn(x_test=X_test, get=kernel_type, compute_cov=compute_cov)
         return pred_mean, pred_cov
 
-    init_fn, apply_fn, kernel_fn = build_kernel_fn(getattr(args, "n_relu", 1))
+    init_fn, apply_fn, kernel_fn = kernel_fn_from_args(args)
     kernel_fn = batch(kernel_fn, device_count=0, batch_size=0)
     start = datetime.datetime.now()
     predict_fn = nt_predict.gradient_descent_mse_ensemble(kernel_fn, X_train, Y_train, diag_reg=1e-3)
@@ -112,7 +132,9 @@ def make_parser():
     # additions (config 1 of BASELINE.json is not reachable from the reference CLI)
     parser.add_argument("--max_num_train", type=int, default=None)
     parser.add_argument("--max_num_test", type=int, default=None)
-    parser.add_argument("--n_relu", type=int, default=1, help="hidden ReLU layers (reference: 1)")
+    parser.add_argument("--n_relu", type=int, default=1, help="hidden layers (reference: 1)")
+    parser.add_argument("--activation", type=str, default="relu", choices=ACTIVATIONS, help="activation of every hidden layer")
+    parser.add_argument("--leaky_alpha", type=float, default=0.1, help="negative slope of --activation leaky_relu")
     parser.add_argument("--full_cov", action='store_true', help="form the full M x M covariance like the reference")
     return parser
 
