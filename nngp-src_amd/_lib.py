@@ -45,6 +45,10 @@ GP_ABI_SYMBOLS = (
 ACT_ABI_SYMBOLS = ("nngp_kernel_build_act", "nngp_kernel_diag_act", "nngp_model_create_act")
 ACT_RELU, ACT_ABRELU, ACT_ERF = 0, 1, 2
 
+# include/nngp_mll.h: the NNGP marginal likelihood and its gradient; GPU library only (no host build)
+MLL_ABI_SYMBOLS = ("nngp_mll_create", "nngp_mll_destroy", "nngp_mll_set_train", "nngp_mll_evaluate", "nngp_mll_terms",
+                   "nngp_mll_factor_buffer")
+
 
 class NngpArch(ctypes.Structure):
     _fields_ = [("n_dense", ctypes.c_int32), ("reserved", ctypes.c_int32),
@@ -91,6 +95,7 @@ def load(knobs: bool = False):
     bind_prototypes(lib, knobs)
     bind_gp_prototypes(lib)
     bind_act_prototypes(lib)
+    bind_mll_prototypes(lib)
     _libs[knobs] = lib
     return lib
 
@@ -201,6 +206,20 @@ def bind_act_prototypes(lib):
     lib.nngp_kernel_diag_act.argtypes = [vp, i64, i32, archp, vp, vp, vp]
     lib.nngp_model_create_act.argtypes = [ctypes.POINTER(vp), i64, i64, i32, i32, archp, i32, dbl, i32]
     for name in ACT_ABI_SYMBOLS:
+        getattr(lib, name).restype = ctypes.c_int
+    return lib
+
+
+def bind_mll_prototypes(lib):
+    """Argument and result types of include/nngp_mll.h (the HIP library only)."""
+    vp, i64, i32, dbl = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_double
+    lib.nngp_mll_create.argtypes = [ctypes.POINTER(vp), i64, i32]
+    lib.nngp_mll_destroy.argtypes = [vp]
+    lib.nngp_mll_set_train.argtypes = [vp, vp, vp, i64, i32, vp]
+    lib.nngp_mll_evaluate.argtypes = [vp, ctypes.POINTER(NngpArchAct), dbl, i32, ctypes.POINTER(dbl), ctypes.POINTER(dbl), vp]
+    lib.nngp_mll_terms.argtypes = [vp, ctypes.POINTER(dbl), i32]
+    lib.nngp_mll_factor_buffer.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(i64), ctypes.POINTER(i64)]
+    for name in MLL_ABI_SYMBOLS:
         getattr(lib, name).restype = ctypes.c_int
     return lib
 

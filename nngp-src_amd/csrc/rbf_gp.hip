@@ -28,22 +28,6 @@ constexpr int NB = TB;        // diagonal block of the Cholesky (the GEMM's tile
 constexpr int SLD = NB + 1;
 constexpr int NPART = 4;      // partial sums per gradient workgroup
 
-// Workgroup b runs on XCD b % 8: deal each XCD a contiguous range of the tile order, so that neighbouring tiles (which share
-// row panels of X) meet in one L2 -- the ordering of gemm_f64.hip / kernel_build.hip.
-__device__ __forceinline__ int64_t xcd_tile(int64_t b, int64_t total) {
-    const int64_t q = total >> 3, r = total & 7, x = b & 7, slot = b >> 3;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + slot;
-}
-
-// lower tile t (row-major over the lower triangle) -> (ti, tj), tj <= ti
-__device__ __forceinline__ void lower_tile(int64_t t, int64_t* ti, int64_t* tj) {
-    int64_t i = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-    while (i * (i + 1) / 2 > t) --i;
-    while ((i + 1) * (i + 2) / 2 <= t) ++i;
-    *ti = i;
-    *tj = t - i * (i + 1) / 2;
-}
-
 // Squared distances of the scaled rows for the 16 entries of this thread: rows i0 + tr + 16 p, columns j0 + tc + 16 q.
 // The features are summed in order k = 0 .. d-1 (as a plain reduction over the last axis does).
 __device__ __forceinline__ void tile_sqdist(const double* x1, int64_t n1, const double* x2, int64_t n2, int d, double ls,
@@ -191,61 +175,6 @@ __global__ __launch_bounds__(256) void k_chol_diag(double* a, int64_t ld, int64_
 
 constexpr size_t kDiagLds = sizeof(double) * (NB * SLD + NB);
 
-// B^T (r rows of length np) <- B^T L^-T.  tri: B^T is the identity, so the result (L^-T) is upper triangular and block step kb only
-// touches rows < (kb + 1) NB.  t: r x NB scratch.
-int trsm_fwd_f64(double* bt, int64_t ldb, int64_t r, const double* l, int64_t ldl, const double* dinv, int64_t np, double* t,
-                 bool tri, hipStream_t s) {
-    for (int64_t kb = 0; kb * NB < np; ++kb) {
-        const int64_t m = tri ? (kb + 1) * NB : r;
-        double* col = bt + kb * NB;
-        const double* di = dinv + kb * NB * NB;
-        if (kb == 0) {  // in place: each output row tile is read (k = 128) only by the workgroup that writes it
-            NNGP_TRY(launch_gemm_nt_f64(col, ldb, nullptr, 0, col, ldb, di, NB, m, NB, NB, 1.0, 0.0, s));
-        } else {
-            NNGP_TRY(launch_gemm_nt_f64(t, NB, col, ldb, bt, ldb, l + kb * NB * ldl, ldl, m, NB, kb * NB, -1.0, 1.0, s));
-            NNGP_TRY(launch_gemm_nt_f64(col, ldb, nullptr, 0, t, NB, di, NB, m, NB, NB, 1.0, 0.0, s));
-        }
-    }
-    return 0;
-}
-
-__global__ __launch_bounds__(256) void k_eye(double* a, int64_t ld, int64_t n) {
-    const int64_t i = blockIdx.y, j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (j < n) a[i * ld + j] = i == j ? 1.0 : 0.0;
-}
-
-// fixed-order block sum of 256 values (thread 0 holds the result)
-__device__ __forceinline__ double block_sum(double v, double* red) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
-// per row: dot[row] = dot_add + sum_k m[row, k] v[k];  sq[row] = sq_from - sum_k m[row, k]^2  (either may be NULL)
-__global__ __launch_bounds__(256) void k_rowdot(const double* m, int64_t ld, int64_t cols, const double* v, double* dot,
-                                               double dot_add, double* sq, double sq_from) {
-    __shared__ double red[256];
-    const double* row = m + (int64_t)blockIdx.x * ld;
-    double a = 0.0, b = 0.0;
-    for (int64_t k = threadIdx.x; k < cols; k += 256) {
-        const double x = row[k];
-        if (dot) a += x * v[k];
-        b += x * x;
-    }
-    a = block_sum(a, red);
-    b = block_sum(b, red);
-    if (threadIdx.x == 0) {
-        if (dot) dot[blockIdx.x] = dot_add + a;
-        if (sq) sq[blockIdx.x] = sq_from - b;
-    }
-}
-
 // One lower tile of the n x n training matrix: with K and the scaled squared distance d2 recomputed,
 //   part[0] = sum alpha_i alpha_j K_ij,  part[1] = sum Ainv_ij K_ij,  part[2] = sum alpha_i alpha_j K_ij d2_ij,  part[3] = sum Ainv_ij K_ij d2_ij
 // over the whole square (off-diagonal entries of the lower triangle count twice).
@@ -309,6 +238,49 @@ __global__ __launch_bounds__(256) void k_gp_finish(const double* l, int64_t ldl,
 }
 
 }  // namespace
+
+// shared with nngp_mll.hip (declared in common.h)
+// B^T (r rows of length np) <- B^T L^-T.  tri: B^T is the identity, so the result (L^-T) is upper triangular and block step kb only
+// touches rows < (kb + 1) NB.  t: r x NB scratch.
+int trsm_fwd_f64(double* bt, int64_t ldb, int64_t r, const double* l, int64_t ldl, const double* dinv, int64_t np, double* t,
+                 bool tri, hipStream_t s) {
+    for (int64_t kb = 0; kb * NB < np; ++kb) {
+        const int64_t m = tri ? (kb + 1) * NB : r;
+        double* col = bt + kb * NB;
+        const double* di = dinv + kb * NB * NB;
+        if (kb == 0) {  // in place: each output row tile is read (k = 128) only by the workgroup that writes it
+            NNGP_TRY(launch_gemm_nt_f64(col, ldb, nullptr, 0, col, ldb, di, NB, m, NB, NB, 1.0, 0.0, s));
+        } else {
+            NNGP_TRY(launch_gemm_nt_f64(t, NB, col, ldb, bt, ldb, l + kb * NB * ldl, ldl, m, NB, kb * NB, -1.0, 1.0, s));
+            NNGP_TRY(launch_gemm_nt_f64(col, ldb, nullptr, 0, t, NB, di, NB, m, NB, NB, 1.0, 0.0, s));
+        }
+    }
+    return 0;
+}
+
+__global__ __launch_bounds__(256) void k_eye(double* a, int64_t ld, int64_t n) {
+    const int64_t i = blockIdx.y, j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j < n) a[i * ld + j] = i == j ? 1.0 : 0.0;
+}
+
+// per row: dot[row] = dot_add + sum_k m[row, k] v[k];  sq[row] = sq_from - sum_k m[row, k]^2  (either may be NULL)
+__global__ __launch_bounds__(256) void k_rowdot(const double* m, int64_t ld, int64_t cols, const double* v, double* dot,
+                                               double dot_add, double* sq, double sq_from) {
+    __shared__ double red[256];
+    const double* row = m + (int64_t)blockIdx.x * ld;
+    double a = 0.0, b = 0.0;
+    for (int64_t k = threadIdx.x; k < cols; k += 256) {
+        const double x = row[k];
+        if (dot) a += x * v[k];
+        b += x * x;
+    }
+    a = block_sum(a, red);
+    b = block_sum(b, red);
+    if (threadIdx.x == 0) {
+        if (dot) dot[blockIdx.x] = dot_add + a;
+        if (sq) sq[blockIdx.x] = sq_from - b;
+    }
+}
 
 int potrf_f64(double* a, int64_t n, int64_t ld, double* dinv, int* status, hipStream_t s) {
     NNGP_REQUIRE(a != nullptr && dinv != nullptr && status != nullptr, "potrf_f64: NULL argument");

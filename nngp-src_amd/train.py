@@ -49,15 +49,17 @@ def kernel_fn_from_args(args):
     return build_kernel_fn(getattr(args, "n_relu", 1), getattr(args, "activation", "relu"), getattr(args, "leaky_alpha", 0.1))
 
 
-def NNGP_train_and_test(args, X_train, Y_train, X_test, Y_test, query_infos_train=None, query_infos_test=None):
+def NNGP_train_and_test(args, X_train, Y_train, X_test, Y_test, query_infos_train=None, query_infos_test=None,
+                        kernel_fn=None, diag_reg=1e-3):
     def prediction(pred_fn, X_test, kernel_type="nngp", compute_cov=True):
         pred_mean, pred_cov = pred_fn(x_test=X_test, get=kernel_type, compute_cov=compute_cov)
         return pred_mean, pred_cov
 
-    init_fn, apply_fn, kernel_fn = kernel_fn_from_args(args)
+    if kernel_fn is None:
+        init_fn, apply_fn, kernel_fn = kernel_fn_from_args(args)
     kernel_fn = batch(kernel_fn, device_count=0, batch_size=0)
     start = datetime.datetime.now()
-    predict_fn = nt_predict.gradient_descent_mse_ensemble(kernel_fn, X_train, Y_train, diag_reg=1e-3)
+    predict_fn = nt_predict.gradient_descent_mse_ensemble(kernel_fn, X_train, Y_train, diag_reg=diag_reg)
     duration = (datetime.datetime.now() - start).total_seconds()
     print('Kernel construction in %s seconds.' % duration)
 
@@ -100,7 +102,20 @@ def load_training_data(args):
     return X, Y, all_query_infos
 
 
+def tune_kernel_fn(args, X_train, Y_train):
+    """--tune_hyper STEPS: W_std / b_std / diag_reg of the NNGP by marginal likelihood on the training split (mll.py)."""
+    from . import mll
+    _, _, kernel_fn = kernel_fn_from_args(args)
+    kernel_fn, diag_reg, _ = mll.tune_hyperparameters(kernel_fn, X_train, Y_train, diag_reg=1e-3, steps=args.tune_hyper,
+                                                      lr=args.tune_lr, b_std_init=args.b_std_init)
+    print("Tuned W_std={} b_std={} diag_reg={}".format(list(kernel_fn.w_std), list(kernel_fn.b_std), diag_reg))
+    return kernel_fn, diag_reg
+
+
 def main(args):
+    tune = getattr(args, "tune_hyper", 0) or 0
+    if tune and args.kernel_type != 'nngp':
+        raise ValueError("--tune_hyper tunes the NNGP posterior's marginal likelihood: it needs --kernel_type nngp")
     if args.join_query:
         raise NotImplementedError("join schemas need their benchmark CSVs; use Estimator(encoder=...)")
     X, Y, all_query_infos = load_training_data(args)
@@ -115,6 +130,10 @@ def main(args):
         from .gp import GP_train_and_test
         return GP_train_and_test(X_train, Y_train, X_test, Y_test, qi_train, qi_test,
                                  cov="full" if getattr(args, "full_cov", False) else "diag", pred_stat=pred_stat)
+    if tune:
+        kernel_fn, diag_reg = tune_kernel_fn(args, X_train, Y_train)
+        return NNGP_train_and_test(args, X_train, Y_train, X_test, Y_test, qi_train, qi_test, kernel_fn=kernel_fn,
+                                   diag_reg=diag_reg)
     return NNGP_train_and_test(args, X_train, Y_train, X_test, Y_test, qi_train, qi_test)
 
 
@@ -136,6 +155,10 @@ def make_parser():
     parser.add_argument("--activation", type=str, default="relu", choices=ACTIVATIONS, help="activation of every hidden layer")
     parser.add_argument("--leaky_alpha", type=float, default=0.1, help="negative slope of --activation leaky_relu")
     parser.add_argument("--full_cov", action='store_true', help="form the full M x M covariance like the reference")
+    parser.add_argument("--tune_hyper", type=int, default=0,
+                        help="steps of marginal-likelihood tuning of W_std / b_std / diag_reg before the fit (nngp only; 0: off)")
+    parser.add_argument("--tune_lr", type=float, default=0.05, help="step size of --tune_hyper")
+    parser.add_argument("--b_std_init", type=float, default=None, help="start of b_std for layers with b_std = 0 (--tune_hyper)")
     return parser
 
 
