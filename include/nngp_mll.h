@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-/* Everything is float64 and has its own factorisation (the float64 Cholesky of nngp_rbf_gp.h); the NNGP model is not
+/* Everything is float64 and has its own factorisation (the float64 Cholesky behind nngp_potrf_f64); the NNGP model is not
  * involved.  The handle holds A / L, L^-T and A^-1 (3 Np^2 doubles, Np = n_cap rounded up to 128), the row norms, y,
  * alpha, w = L^-1 y and the gradient partials.  No device allocation after create.  One handle is driven from one stream
  * at a time. */

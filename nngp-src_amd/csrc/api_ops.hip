@@ -1,6 +1,7 @@
 // Stand-alone operator entry points of the C ABI (no model object): the factorisation, the GEMMs, pool selection, the ticket tables --
 // what tests/, scripts/ and the multi-GPU drivers call directly.
 #include "model.h"
+#include "gp_f64.h"
 
 extern "C" {
 

@@ -157,46 +157,6 @@ int launch_gemm_nt_h3x(float* c, int64_t ldc, const char* a, const char* b, int6
 // ---- potrf.hip ----
 int launch_potrf_leaf(float* a, int64_t ld, float* dinv_block, int32_t* clamped, float pivot_floor, hipStream_t s);
 int potrf_f32(float* a, int64_t n, int64_t ld, float* dinv, int32_t* clamped, float pivot_floor, hipStream_t s);
-// ---- rbf_gp.hip: float64 blocked Cholesky (n multiple of 128; dinv: n x 128; status: device int, -1 or the failed column) ----
-int potrf_f64(double* a, int64_t n, int64_t ld, double* dinv, int* status, hipStream_t s);
-int potrf_f64_status(const int* status, hipStream_t s, const char* who);  // syncs; rc < 0 naming the column if a pivot failed
-// also from rbf_gp.hip, shared with nngp_mll.hip:
-// B^T (r rows of length np) <- B^T L^-T (tri: B^T is the identity); t: r x 128 scratch
-int trsm_fwd_f64(double* bt, int64_t ldb, int64_t r, const double* l, int64_t ldl, const double* dinv, int64_t np, double* t,
-                 bool tri, hipStream_t s);
-__global__ __launch_bounds__(256) void k_eye(double* a, int64_t ld, int64_t n);  // grid (ceil(n / 256), rows)
-// per row: dot[row] = dot_add + sum_k m[row, k] v[k];  sq[row] = sq_from - sum_k m[row, k]^2  (either may be NULL)
-__global__ __launch_bounds__(256) void k_rowdot(const double* m, int64_t ld, int64_t cols, const double* v, double* dot,
-                                               double dot_add, double* sq, double sq_from);
-
-// Workgroup b runs on XCD b % 8: deal each XCD a contiguous range of the tile order, so that neighbouring tiles (which share
-// row panels of X) meet in one L2 -- the ordering of gemm_f64.hip / kernel_build.hip.
-__device__ __forceinline__ int64_t xcd_tile(int64_t b, int64_t total) {
-    const int64_t q = total >> 3, r = total & 7, x = b & 7, slot = b >> 3;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + slot;
-}
-
-// lower tile t (row-major over the lower triangle) -> (ti, tj), tj <= ti
-__device__ __forceinline__ void lower_tile(int64_t t, int64_t* ti, int64_t* tj) {
-    int64_t i = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-    while (i * (i + 1) / 2 > t) --i;
-    while ((i + 1) * (i + 2) / 2 <= t) ++i;
-    *ti = i;
-    *tj = t - i * (i + 1) / 2;
-}
-
-// fixed-order block sum of 256 values (thread 0 holds the result)
-__device__ __forceinline__ double block_sum(double v, double* red) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
 int trsm_rlt_f32(float* b, int64_t ldb, int64_t m, const float* l, int64_t ldl, const float* dinv, int64_t n,
                  hipStream_t s);
 

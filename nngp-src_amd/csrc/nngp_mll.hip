@@ -4,7 +4,7 @@
 //
 // Everything is float64 and factors on its own (the float32 factor of the NNGP fit gives neither log det A nor tr(A^-1 dA) to
 // float64 grade): K is built by the kernel build (launch_kernel_build, per-layer recursion, no composite
-// map), then the float64 blocked Cholesky, triangular solves and explicit inverse of rbf_gp.hip.
+// map), then the float64 core of gp_f64.h factors it and forms w, A^-1 and alpha, as for the RBF GP.
 //
 //   k_mll_pad            identity on the padding rows / columns of A (n .. Np)
 //   k_mll_diag           tr K (fixed order) and r = lambda tr K / N (or lambda) added to the diagonal
@@ -16,7 +16,7 @@
 //   k_mll_finish         one workgroup, fixed order: the partial vectors, sum log L_ii, |w|^2, alpha^T alpha, tr A^-1 and the
 //                        per-layer sums of the diagonal's q chain (tr dK/dtheta follows from them in closed form)
 // No atomics anywhere: repeated evaluations are bit-identical.
-#include "model.h"
+#include "gp_f64.h"
 #include "f64_math.h"
 #include "trig_tab.h"
 
@@ -27,10 +27,9 @@ namespace nngp {
 
 namespace {
 
-constexpr int MT = 64;         // tile edge of the fused gradient pass
+constexpr int MT = kGpTile;    // tile edge of the fused gradient pass
 constexpr int MKC = 32;        // feature chunk staged in LDS
 constexpr int MLD = MKC + 1;   // LDS row stride (odd: the 16 rows a wave reads sit in different banks)
-constexpr int NB = TB;         // padding of A (the float64 Cholesky's block)
 constexpr double kPi = 3.14159265358979323846;
 constexpr int kMaxComp = 2 * NNGP_MAX_DENSE;  // gradient components of K
 constexpr int kRed = 8;                       // scalar sums of k_mll_diag / k_mll_finish (see nngp_mll::red)
@@ -230,34 +229,26 @@ __global__ __launch_bounds__(256) void k_mll_finish(const double* l, int64_t ldl
                                                     int64_t nparts, const double* alpha, const double* ainv, const double* q,
                                                     ArchDev arch, double* out) {
     __shared__ double red[256];
+    double s[4];
+    finish_sums(l, ldl, n, w, alpha, ainv, red, s);
+    if (threadIdx.x == 0)
+        for (int c = 0; c < 4; ++c) out[c] = s[c];
+    if (!alpha) return;
     const int nd = arch.n_dense;
-    double v[4] = {0.0, 0.0, 0.0, 0.0};
     double sq[NNGP_MAX_DENSE];
 #pragma unroll
     for (int e = 0; e < NNGP_MAX_DENSE; ++e) sq[e] = 0.0;
     for (int64_t i = threadIdx.x; i < n; i += 256) {
-        v[0] += log(l[i * ldl + i]);
-        v[1] += w[i] * w[i];
-        if (alpha) {
-            v[2] += alpha[i] * alpha[i];
-            v[3] += ainv[i * ldl + i];
-            double z = q[i];
+        double z = q[i];
 #pragma unroll
-            for (int e = 0; e < NNGP_MAX_DENSE; ++e) {
-                if (e < nd) {
-                    sq[e] += z;
-                    const double zp = fma(arch.w2[e], z, arch.b2[e]);
-                    if (e < nd - 1) z = arch.act[e] == NNGP_ACT_ABRELU ? arch.ap[e][2] * zp : 0.5 * zp;
-                }
+        for (int e = 0; e < NNGP_MAX_DENSE; ++e) {
+            if (e < nd) {
+                sq[e] += z;
+                const double zp = fma(arch.w2[e], z, arch.b2[e]);
+                if (e < nd - 1) z = arch.act[e] == NNGP_ACT_ABRELU ? arch.ap[e][2] * zp : 0.5 * zp;
             }
         }
     }
-    const int nv = alpha ? 4 : 2;
-    for (int c = 0; c < nv; ++c) {
-        const double r = block_sum(v[c], red);
-        if (threadIdx.x == 0) out[c] = r;
-    }
-    if (!alpha) return;
 #pragma unroll
     for (int e = 0; e < NNGP_MAX_DENSE; ++e) {
         if (e < nd) {
@@ -266,16 +257,9 @@ __global__ __launch_bounds__(256) void k_mll_finish(const double* l, int64_t ldl
         }
     }
     for (int c = 0; c < 4 * nd; ++c) {
-        double s = 0.0;
-        for (int64_t b = threadIdx.x; b < nparts; b += 256) s += part[(int64_t)c * nparts + b];
-        const double r = block_sum(s, red);
+        const double r = finish_part(part, nparts, c, red);
         if (threadIdx.x == 0) out[4 + nd + c] = r;
     }
-}
-
-int64_t mll_nparts(int64_t n) {
-    const int64_t tn = (n + MT - 1) / MT;
-    return tn * (tn + 1) / 2;
 }
 
 int launch_mll_partial(const MllArgs& a, const ArchDev& arch, hipStream_t s) {
@@ -299,47 +283,18 @@ using namespace nngp;
 // C ABI (include/nngp_mll.h)
 
 struct nngp_mll {
-    int64_t n_cap = 0, np_cap = 0;
-    int d = 0;
-    int64_t n = 0, np = 0;
+    GpWorkspace w;            // part: 2 kMaxComp per tile; red: [0, 2) tr K, r; [kRed, ...) k_mll_finish's sums
+    double* q = nullptr;      // n_cap: |x_i|^2 / d
     int n_dense = 0;
-    bool have_train = false, factored = false, have_terms = false;
+    bool have_terms = false;
     double terms[2 * (kMaxComp + 1) + 5 + kMaxComp] = {};
     int n_terms = 0;
-    double* x = nullptr;      // n_cap x d
-    double* q = nullptr;      // n_cap: |x_i|^2 / d
-    double* y = nullptr;      // np_cap, zero padded
-    double* a = nullptr;      // np_cap^2: A, then its factor L (lower)
-    double* zt = nullptr;     // np_cap^2: L^-T
-    double* ainv = nullptr;   // np_cap^2: A^-1 = L^-T L^-1
-    double* dinv = nullptr;   // np_cap x NB: inverted diagonal blocks
-    double* wrow = nullptr;   // NB x np_cap: row 0 = y, solved in place to w = L^-1 y; the other rows stay 0
-    double* alpha = nullptr;  // np_cap
-    double* part = nullptr;   // 2 kMaxComp x nparts(n_cap): gradient partials
-    double* red = nullptr;    // [0, 2): tr K, r; [kRed, ...): k_mll_finish's sums
-    int* status = nullptr;
-    double* t = nullptr;      // np_cap x NB solve scratch
 };
 
-namespace {
-
-void mll_free(nngp_mll* h) {
-    dev_free(h->x);
+static void mll_free(nngp_mll* h) {
     dev_free(h->q);
-    dev_free(h->y);
-    dev_free(h->a);
-    dev_free(h->zt);
-    dev_free(h->ainv);
-    dev_free(h->dinv);
-    dev_free(h->wrow);
-    dev_free(h->alpha);
-    dev_free(h->part);
-    dev_free(h->red);
-    dev_free(h->status);
-    dev_free(h->t);
+    ws_free(&h->w);
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -348,23 +303,8 @@ int nngp_mll_create(nngp_mll** out, int64_t n_cap, int32_t d) {
     *out = nullptr;
     nngp_mll* h = new (std::nothrow) nngp_mll();
     NNGP_REQUIRE(h != nullptr, "mll_create: out of host memory");
-    h->n_cap = n_cap;
-    h->d = d;
-    h->np_cap = round_up(n_cap, NB);
-    const int64_t np = h->np_cap;
-    int rc = dev_alloc(&h->x, n_cap * d);
-    if (rc == 0) rc = dev_alloc(&h->q, n_cap);
-    if (rc == 0) rc = dev_alloc(&h->y, np);
-    if (rc == 0) rc = dev_alloc(&h->a, np * np);
-    if (rc == 0) rc = dev_alloc(&h->zt, np * np);
-    if (rc == 0) rc = dev_alloc(&h->ainv, np * np);
-    if (rc == 0) rc = dev_alloc(&h->dinv, np * NB);
-    if (rc == 0) rc = dev_alloc(&h->wrow, NB * np);
-    if (rc == 0) rc = dev_alloc(&h->alpha, np);
-    if (rc == 0) rc = dev_alloc(&h->part, 2 * kMaxComp * mll_nparts(n_cap));
-    if (rc == 0) rc = dev_alloc(&h->red, kRed + 4 + NNGP_MAX_DENSE + 2 * kMaxComp);
-    if (rc == 0) rc = dev_alloc(&h->status, 1);
-    if (rc == 0) rc = dev_alloc(&h->t, np * NB);
+    int rc = dev_alloc(&h->q, n_cap);
+    if (rc == 0) rc = ws_alloc(&h->w, n_cap, d, 2 * kMaxComp, kRed + 4 + NNGP_MAX_DENSE + 2 * kMaxComp, round_up(n_cap, TB));
     if (rc != 0) {
         mll_free(h);
         delete h;
@@ -386,25 +326,17 @@ int nngp_mll_set_train(nngp_mll* h, const double* x, const double* y, int64_t n,
     hipStream_t s = (hipStream_t)stream;
     NNGP_REQUIRE(h != nullptr && x != nullptr && y != nullptr, "mll_set_train: NULL argument");
     NNGP_REQUIRE(ny == 1, "mll_set_train: the marginal likelihood takes one output column (ny=%d)", ny);
-    NNGP_REQUIRE(n >= 1 && n <= h->n_cap, "mll_set_train: n=%lld outside [1, n_cap=%lld]", (long long)n, (long long)h->n_cap);
-    h->have_train = h->factored = h->have_terms = false;
-    h->n = n;
-    h->np = round_up(n, NB);
-    NNGP_HIP_CHECK(hipMemcpyAsync(h->x, x, sizeof(double) * n * h->d, hipMemcpyDeviceToDevice, s));
-    NNGP_TRY(launch_row_sqnorm(h->x, n, h->d, h->q, s));
-    NNGP_HIP_CHECK(hipMemsetAsync(h->y, 0, sizeof(double) * h->np, s));
-    NNGP_HIP_CHECK(hipMemcpyAsync(h->y, y, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
-    NNGP_HIP_CHECK(hipMemsetAsync(h->wrow, 0, sizeof(double) * NB * h->np, s));
-    NNGP_HIP_CHECK(hipStreamSynchronize(s));
-    h->have_train = true;
-    return 0;
+    NNGP_REQUIRE(n >= 1 && n <= h->w.n_cap, "mll_set_train: n=%lld outside [1, n_cap=%lld]", (long long)n, (long long)h->w.n_cap);
+    h->have_terms = false;
+    NNGP_TRY(launch_row_sqnorm(x, n, h->w.d, h->q, s));  // from the caller's x: ws_set_train's synchronise covers it
+    return ws_set_train(&h->w, x, y, hipMemcpyDeviceToDevice, n, s);
 }
 
 int nngp_mll_evaluate(nngp_mll* h, const nngp_arch_act* arch_in, double diag_reg, int32_t absolute, double* nlml, double* grad,
                       void* stream) {
     hipStream_t s = (hipStream_t)stream;
     NNGP_REQUIRE(h != nullptr && arch_in != nullptr && nlml != nullptr, "mll_evaluate: NULL argument");
-    NNGP_REQUIRE(h->have_train, "mll_evaluate: no training data (nngp_mll_set_train)");
+    NNGP_REQUIRE(h->w.n > 0, "mll_evaluate: no training data (nngp_mll_set_train)");
     ArchDev arch{};
     NNGP_TRY(make_arch_dev_act(arch_in, &arch));
     const int nd = arch.n_dense;
@@ -416,52 +348,44 @@ int nngp_mll_evaluate(nngp_mll* h, const nngp_arch_act* arch_in, double diag_reg
     for (int l = 0; l < nd - 1; ++l)
         NNGP_REQUIRE(arch.act[l] != NNGP_ACT_ERF, "mll_evaluate: hidden layer %d is Erf; the gradient covers ReLU and ABRelu only", l);
     NNGP_REQUIRE(std::isfinite(diag_reg) && diag_reg >= 0.0, "mll_evaluate: diag_reg must be finite and non-negative (%g)", diag_reg);
-    h->factored = h->have_terms = false;
-    const int64_t n = h->n, np = h->np;
+    GpWorkspace& w = h->w;
+    w.factored = h->have_terms = false;
+    const int64_t n = w.n, np = w.np;
 
     // A = K + r I: K by the kernel build (per-layer recursion: no_comp), the padding the identity
     BuildArgs b{};
-    b.x1 = b.x2 = h->x;
+    b.x1 = b.x2 = w.x;
     b.q1 = b.q2 = h->q;
     b.n1 = b.n2 = n;
-    b.d = h->d;
+    b.d = w.d;
     b.row_begin = 0;
     b.row_end = n;
     b.sym = 1;
-    b.nngp64 = h->a;
+    b.nngp64 = w.a;
     b.ld64 = np;
     b.no_comp = 1;
     NNGP_TRY(launch_kernel_build(b, arch, s));
-    hipLaunchKernelGGL(k_mll_pad, dim3((unsigned)np), dim3(256), 0, s, h->a, np, n, np);
-    hipLaunchKernelGGL(k_mll_diag, dim3(1), dim3(256), 0, s, h->a, np, n, diag_reg, (int)(absolute != 0), h->red);
+    hipLaunchKernelGGL(k_mll_pad, dim3((unsigned)np), dim3(256), 0, s, w.a, np, n, np);
+    hipLaunchKernelGGL(k_mll_diag, dim3(1), dim3(256), 0, s, w.a, np, n, diag_reg, (int)(absolute != 0), w.red);
     NNGP_HIP_CHECK(hipGetLastError());
-    NNGP_TRY(potrf_f64(h->a, np, np, h->dinv, h->status, s));
-    NNGP_TRY(potrf_f64_status(h->status, s, "mll_evaluate"));
-    NNGP_HIP_CHECK(hipMemcpyAsync(h->wrow, h->y, sizeof(double) * np, hipMemcpyDeviceToDevice, s));
-    NNGP_TRY(trsm_fwd_f64(h->wrow, np, NB, h->a, np, h->dinv, np, h->t, false, s));
     const bool want = grad != nullptr;
-    const int64_t nparts = mll_nparts(n);
+    NNGP_TRY(factor_and_solve(&w, want, "mll_evaluate", s));
+    const int64_t nparts = gp_lower_tiles(n);
     if (want) {
-        hipLaunchKernelGGL(k_eye, dim3((unsigned)((np + 255) / 256), (unsigned)np), dim3(256), 0, s, h->zt, np, np);
-        NNGP_HIP_CHECK(hipGetLastError());
-        NNGP_TRY(trsm_fwd_f64(h->zt, np, np, h->a, np, h->dinv, np, h->t, true, s));
-        NNGP_TRY(launch_gemm_nt_f64(h->ainv, np, nullptr, 0, h->zt, np, h->zt, np, np, np, np, 1.0, 0.0, s));
-        hipLaunchKernelGGL(k_rowdot, dim3((unsigned)np), dim3(256), 0, s, h->zt, np, np, h->wrow, h->alpha, 0.0, nullptr, 0.0);
-        NNGP_HIP_CHECK(hipGetLastError());
-        MllArgs ma{h->x, h->q, n, h->d, h->ainv, np, h->alpha, h->part, nparts};
+        MllArgs ma{w.x, h->q, n, w.d, w.ainv, np, w.alpha, w.part, nparts};
         NNGP_TRY(launch_mll_partial(ma, arch, s));
     }
-    hipLaunchKernelGGL(k_mll_finish, dim3(1), dim3(256), 0, s, h->a, np, n, h->wrow, want ? h->part : nullptr, nparts,
-                       want ? h->alpha : nullptr, h->ainv, h->q, arch, h->red + kRed);
+    hipLaunchKernelGGL(k_mll_finish, dim3(1), dim3(256), 0, s, w.a, np, n, w.wrow, want ? w.part : nullptr, nparts,
+                       want ? w.alpha : nullptr, w.ainv, h->q, arch, w.red + kRed);
     NNGP_HIP_CHECK(hipGetLastError());
     double r[kRed + 4 + NNGP_MAX_DENSE + 2 * kMaxComp];
-    NNGP_HIP_CHECK(hipMemcpyAsync(r, h->red, sizeof(r), hipMemcpyDeviceToHost, s));
+    NNGP_HIP_CHECK(hipMemcpyAsync(r, w.red, sizeof(r), hipMemcpyDeviceToHost, s));
     NNGP_HIP_CHECK(hipStreamSynchronize(s));
     const double tr_k = r[0], logdet_half = r[kRed], yay = r[kRed + 1];
     const double dn = (double)n;
     *nlml = 0.5 * yay + logdet_half + 0.5 * dn * log(2.0 * kPi);
     h->n_dense = nd;
-    h->factored = true;
+    w.factored = true;
     if (!want) return 0;
     const double aa = r[kRed + 2], tr_ainv = r[kRed + 3];
     const double* sq = r + kRed + 4;
@@ -516,10 +440,10 @@ int nngp_mll_terms(const nngp_mll* h, double* out, int32_t count) {
 
 int nngp_mll_factor_buffer(const nngp_mll* h, double** l, int64_t* ld, int64_t* n_padded) {
     NNGP_REQUIRE(h != nullptr && l != nullptr && ld != nullptr, "mll_factor_buffer: NULL argument");
-    NNGP_REQUIRE(h->factored, "mll_factor_buffer: no factor (nngp_mll_evaluate)");
-    *l = h->a;
-    *ld = h->np;
-    if (n_padded) *n_padded = h->np;
+    NNGP_REQUIRE(h->w.factored, "mll_factor_buffer: no factor (nngp_mll_evaluate)");
+    *l = h->w.a;
+    *ld = h->w.np;
+    if (n_padded) *n_padded = h->w.np;
     return 0;
 }
 

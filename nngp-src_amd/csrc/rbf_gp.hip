@@ -1,19 +1,14 @@
 // float64 RBF Gaussian process with marginal-likelihood training (reference train.py:60-150, GP_train_and_test).
 //
 // Everything here is float64, like the reference (train.py:24): the kernel matrix A = amp K + (noise + 1e-6) I, its
-// Cholesky factor, log det A = 2 sum log L_ii, alpha = A^-1 y and A^-1 itself for the gradient's trace terms.  The NNGP
-// path's float32 factor cannot give log det A or tr(A^-1 dA) to that grade, so this file has its
-// own factorisation and leaves the NNGP model untouched.
+// Cholesky factor, log det A = 2 sum log L_ii, alpha = A^-1 y and A^-1 itself for the gradient's trace terms.  The factor,
+// the solves and A^-1 are the float64 core of gp_f64.h, shared with the NNGP marginal likelihood; the NNGP model is untouched.
 //
 //   k_rbf_tile        K(i, j) = exp(-sum_k (x1_ik / ls - x2_jk / ls)^2) on 64 x 64 tiles, the differences formed directly
 //                     (no Gram identity: raw forest rows have |x|^2 ~ 2e7 and the identity would cancel to ~1e-9)
-//   k_chol_diag       factors one 128 x 128 diagonal block in LDS and writes the block's inverse
-//   potrf_f64         blocked right-looking Cholesky: k_chol_diag, then the panel L21 = A21 L11^-T and the trailing update
-//                     A22 -= L21 L21^T on the float64 MFMA GEMM (gemm_f64.hip)
-//   trsm_fwd_f64      B^T <- B^T L^-T (each row b of B^T becomes L^-1 b), left-looking by 128-column blocks, two GEMMs per block
 //   k_gp_grad_partial one pass over the lower triangle of A^-1 with K recomputed: the four trace / quadratic-form sums
 //   k_gp_finish       fixed-order second stage of every reduction (no atomics: repeated evaluations are bit-identical)
-#include "model.h"
+#include "gp_f64.h"
 
 #include <vector>
 
@@ -21,11 +16,10 @@ namespace nngp {
 
 namespace {
 
-constexpr int RT = 64;        // edge of the kernel-build and gradient tiles
+constexpr int RT = kGpTile;   // edge of the kernel-build and gradient tiles
 constexpr int RKC = 32;       // feature chunk staged in LDS
 constexpr int RLD = RKC + 1;  // LDS row stride (odd: the 16 rows a wave reads sit in different banks)
-constexpr int NB = TB;        // diagonal block of the Cholesky (the GEMM's tile edge)
-constexpr int SLD = NB + 1;
+constexpr int NB = TB;        // padding of the test rows (the Cholesky's block)
 constexpr int NPART = 4;      // partial sums per gradient workgroup
 
 // Squared distances of the scaled rows for the 16 entries of this thread: rows i0 + tr + 16 p, columns j0 + tc + 16 q.
@@ -126,55 +120,6 @@ int launch_rbf(RbfArgs a, hipStream_t s) {
     return 0;
 }
 
-// One 128 x 128 diagonal block: L11 = chol(A11) in place (zeros above the diagonal) and dinv = L11^-1 (lower).  A pivot that is
-// not positive (or not finite) stops the factorisation: status <- its global column, and every later block returns at once.
-__global__ __launch_bounds__(256) void k_chol_diag(double* a, int64_t ld, int64_t kb, double* dinv, int* status) {
-    extern __shared__ __attribute__((aligned(16))) double S[];  // NB x SLD, then NB inverted pivots
-    double* invd = S + NB * SLD;
-    if (*status >= 0) return;
-    const int tid = threadIdx.x;
-    double* a0 = a + kb * NB * ld + kb * NB;
-    for (int e = tid; e < NB * NB; e += 256) S[(e / NB) * SLD + e % NB] = a0[(int64_t)(e / NB) * ld + e % NB];
-    __syncthreads();
-    for (int j = 0; j < NB; ++j) {
-        const double p = S[j * SLD + j];
-        if (!(p > 0.0) || !isfinite(p)) {  // uniform: every thread read the same LDS word
-            if (tid == 0) *status = (int)(kb * NB + j);
-            return;
-        }
-        const double ljj = sqrt(p);
-        __syncthreads();
-        if (tid == 0) S[j * SLD + j] = ljj;
-        for (int i = j + 1 + tid; i < NB; i += 256) S[i * SLD + j] = S[i * SLD + j] / ljj;
-        __syncthreads();
-        for (int i = j + 1 + (tid >> 5); i < NB; i += 8) {  // trailing lower triangle: 8 rows x 32 columns per pass
-            const double lij = S[i * SLD + j];
-            for (int k = j + 1 + (tid & 31); k <= i; k += 32) S[i * SLD + k] -= lij * S[k * SLD + j];
-        }
-        __syncthreads();
-    }
-    // L11^-1 by forward substitution, one column per thread: X(i, c) for i > c goes to S(c, i) (the free upper triangle)
-    if (tid < NB) {
-        const int c = tid;
-        const double dc = 1.0 / S[c * SLD + c];
-        invd[c] = dc;
-        for (int i = c + 1; i < NB; ++i) {
-            double sum = S[i * SLD + c] * dc;
-            for (int k = c + 1; k < i; ++k) sum += S[i * SLD + k] * S[c * SLD + k];
-            S[c * SLD + i] = -sum / S[i * SLD + i];
-        }
-    }
-    __syncthreads();
-    double* di = dinv + kb * NB * NB;
-    for (int e = tid; e < NB * NB; e += 256) {
-        const int r = e / NB, c = e % NB;
-        a0[(int64_t)r * ld + c] = c <= r ? S[r * SLD + c] : 0.0;
-        di[e] = r > c ? S[c * SLD + r] : (r == c ? invd[r] : 0.0);
-    }
-}
-
-constexpr size_t kDiagLds = sizeof(double) * (NB * SLD + NB);
-
 // One lower tile of the n x n training matrix: with K and the scaled squared distance d2 recomputed,
 //   part[0] = sum alpha_i alpha_j K_ij,  part[1] = sum Ainv_ij K_ij,  part[2] = sum alpha_i alpha_j K_ij d2_ij,  part[3] = sum Ainv_ij K_ij d2_ij
 // over the whole square (off-diagonal entries of the lower triangle count twice).
@@ -208,112 +153,31 @@ __global__ __launch_bounds__(256) void k_gp_grad_partial(const double* x, int64_
 #pragma unroll
     for (int c = 0; c < NPART; ++c) {
         const double r = block_sum(v[c], red);
-        if (threadIdx.x == 0) part[(int64_t)blockIdx.x * NPART + c] = r;
+        if (threadIdx.x == 0) part[(int64_t)c * gridDim.x + blockIdx.x] = r;  // component-major (finish_part)
     }
 }
 
 // Second stage, one workgroup, fixed order:  out[0] = sum log L_ii,  out[1] = |w|^2 (w = L^-1 y, so y^T A^-1 y),
-// out[2..5] = the gradient partials summed,  out[6] = alpha^T alpha,  out[7] = tr A^-1   (the last five only with grad)
+// out[2..5] = the gradient partials summed,  out[6] = alpha^T alpha,  out[7] = tr A^-1   (the last six only with grad)
 __global__ __launch_bounds__(256) void k_gp_finish(const double* l, int64_t ldl, int64_t n, const double* w, const double* part,
                                                    int64_t nparts, const double* alpha, const double* ainv, double* out) {
     __shared__ double red[256];
-    double v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int64_t i = threadIdx.x; i < n; i += 256) {
-        v[0] += log(l[i * ldl + i]);
-        v[1] += w[i] * w[i];
-        if (alpha) {
-            v[6] += alpha[i] * alpha[i];
-            v[7] += ainv[i * ldl + i];
-        }
+    double s[4];
+    finish_sums(l, ldl, n, w, alpha, ainv, red, s);
+    if (threadIdx.x == 0) {
+        out[0] = s[0];
+        out[1] = s[1];
+        out[6] = s[2];
+        out[7] = s[3];
     }
-    if (part)
-        for (int64_t b = threadIdx.x; b < nparts; b += 256)
-#pragma unroll
-            for (int c = 0; c < NPART; ++c) v[2 + c] += part[b * NPART + c];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        const double r = block_sum(v[c], red);
-        if (threadIdx.x == 0) out[c] = r;
+    if (!part) return;
+    for (int c = 0; c < NPART; ++c) {
+        const double r = finish_part(part, nparts, c, red);
+        if (threadIdx.x == 0) out[2 + c] = r;
     }
 }
 
 }  // namespace
-
-// shared with nngp_mll.hip (declared in common.h)
-// B^T (r rows of length np) <- B^T L^-T.  tri: B^T is the identity, so the result (L^-T) is upper triangular and block step kb only
-// touches rows < (kb + 1) NB.  t: r x NB scratch.
-int trsm_fwd_f64(double* bt, int64_t ldb, int64_t r, const double* l, int64_t ldl, const double* dinv, int64_t np, double* t,
-                 bool tri, hipStream_t s) {
-    for (int64_t kb = 0; kb * NB < np; ++kb) {
-        const int64_t m = tri ? (kb + 1) * NB : r;
-        double* col = bt + kb * NB;
-        const double* di = dinv + kb * NB * NB;
-        if (kb == 0) {  // in place: each output row tile is read (k = 128) only by the workgroup that writes it
-            NNGP_TRY(launch_gemm_nt_f64(col, ldb, nullptr, 0, col, ldb, di, NB, m, NB, NB, 1.0, 0.0, s));
-        } else {
-            NNGP_TRY(launch_gemm_nt_f64(t, NB, col, ldb, bt, ldb, l + kb * NB * ldl, ldl, m, NB, kb * NB, -1.0, 1.0, s));
-            NNGP_TRY(launch_gemm_nt_f64(col, ldb, nullptr, 0, t, NB, di, NB, m, NB, NB, 1.0, 0.0, s));
-        }
-    }
-    return 0;
-}
-
-__global__ __launch_bounds__(256) void k_eye(double* a, int64_t ld, int64_t n) {
-    const int64_t i = blockIdx.y, j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (j < n) a[i * ld + j] = i == j ? 1.0 : 0.0;
-}
-
-// per row: dot[row] = dot_add + sum_k m[row, k] v[k];  sq[row] = sq_from - sum_k m[row, k]^2  (either may be NULL)
-__global__ __launch_bounds__(256) void k_rowdot(const double* m, int64_t ld, int64_t cols, const double* v, double* dot,
-                                               double dot_add, double* sq, double sq_from) {
-    __shared__ double red[256];
-    const double* row = m + (int64_t)blockIdx.x * ld;
-    double a = 0.0, b = 0.0;
-    for (int64_t k = threadIdx.x; k < cols; k += 256) {
-        const double x = row[k];
-        if (dot) a += x * v[k];
-        b += x * x;
-    }
-    a = block_sum(a, red);
-    b = block_sum(b, red);
-    if (threadIdx.x == 0) {
-        if (dot) dot[blockIdx.x] = dot_add + a;
-        if (sq) sq[blockIdx.x] = sq_from - b;
-    }
-}
-
-int potrf_f64(double* a, int64_t n, int64_t ld, double* dinv, int* status, hipStream_t s) {
-    NNGP_REQUIRE(a != nullptr && dinv != nullptr && status != nullptr, "potrf_f64: NULL argument");
-    NNGP_REQUIRE(n > 0 && n % NB == 0 && ld >= n && ld % 2 == 0 && ((uintptr_t)a & 15) == 0,
-                 "potrf_f64: n must be a positive multiple of %d and ld >= n even (n=%lld ld=%lld)", NB, (long long)n, (long long)ld);
-    static std::once_flag once;
-    static hipError_t attr = hipSuccess;
-    std::call_once(once, [] {
-        attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_chol_diag), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kDiagLds);
-    });
-    NNGP_HIP_CHECK(attr);
-    NNGP_HIP_CHECK(hipMemsetAsync(status, 0xff, sizeof(int), s));  // -1: no failed pivot
-    for (int64_t kb = 0; kb * NB < n; ++kb) {
-        hipLaunchKernelGGL(k_chol_diag, dim3(1), dim3(256), kDiagLds, s, a, ld, kb, dinv, status);
-        NNGP_HIP_CHECK(hipGetLastError());
-        const int64_t rem = n - (kb + 1) * NB;
-        if (rem == 0) break;
-        double* a21 = a + (kb + 1) * NB * ld + kb * NB;
-        // panel in place: one column tile, so each row tile of A21 is read only by the workgroup that overwrites it
-        NNGP_TRY(launch_gemm_nt_f64(a21, ld, nullptr, 0, a21, ld, dinv + kb * NB * NB, NB, rem, NB, NB, 1.0, 0.0, s));
-        double* a22 = a21 + NB;
-        NNGP_TRY(launch_gemm_nt_f64(a22, ld, a22, ld, a21, ld, a21, ld, rem, rem, NB, -1.0, 1.0, s));
-    }
-    return 0;
-}
-
-int potrf_f64_status(const int* status, hipStream_t s, const char* who) {
-    int st = -1;
-    NNGP_HIP_CHECK(hipMemcpyAsync(&st, status, sizeof(int), hipMemcpyDeviceToHost, s));
-    NNGP_HIP_CHECK(hipStreamSynchronize(s));
-    NNGP_REQUIRE(st < 0, "%s: the matrix is not positive definite: the pivot of column %d is not positive", who, st);
-    return 0;
-}
 
 }  // namespace nngp
 
@@ -321,36 +185,17 @@ int potrf_f64_status(const int* status, hipStream_t s, const char* who) {
 // C ABI (include/nngp_hip.h, "RBF Gaussian process")
 
 struct nngp_rbf_gp {
-    int64_t n_cap = 0, m_cap = 0, np_cap = 0, mp_cap = 0;
-    int d = 0;
-    int64_t n = 0, np = 0;
+    GpWorkspace w;            // y: y - mean(y); t: max(np_cap, mp_cap) rows
+    int64_t m_cap = 0, mp_cap = 0;
     double ymean = 0.0;
-    bool have_train = false, factored = false, have_terms = false;
+    bool have_terms = false;
     double amp = 0, noise = 0, ls = 0;
     double terms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    double* x = nullptr;      // n_cap x d
-    double* yc = nullptr;     // np_cap: y - mean(y), zero padded
-    double* a = nullptr;      // np_cap^2: A, then its factor L (lower)
-    double* zt = nullptr;     // np_cap^2: L^-T
-    double* ainv = nullptr;   // np_cap^2: A^-1 = L^-T L^-1
-    double* dinv = nullptr;   // np_cap x NB: inverted diagonal blocks
-    double* wrow = nullptr;   // NB x np_cap: row 0 = y, solved in place to w = L^-1 y; the other rows stay 0
-    double* alpha = nullptr;  // np_cap
-    double* part = nullptr;   // gradient partials
-    double* red = nullptr;    // 8 reduced sums
-    int* status = nullptr;
-    double* t = nullptr;      // max(np_cap, mp_cap) x NB solve scratch
     double* cross = nullptr;  // mp_cap x np_cap: amp K(X_t, X), solved in place to V^T
     double* covtmp = nullptr; // mp_cap^2: V^T V
-    int64_t t_rows = 0;
 };
 
 namespace {
-
-int64_t gp_nparts(int64_t n) {
-    const int64_t tn = (n + RT - 1) / RT;
-    return tn * (tn + 1) / 2;
-}
 
 void gp_free_test(nngp_rbf_gp* g) {
     dev_free(g->cross);
@@ -361,31 +206,14 @@ int gp_alloc_test(nngp_rbf_gp* g, int64_t m_cap) {
     gp_free_test(g);
     g->m_cap = m_cap;
     g->mp_cap = round_up(m_cap > 0 ? m_cap : 1, NB);
-    NNGP_TRY(dev_alloc(&g->cross, g->mp_cap * g->np_cap));
+    NNGP_TRY(dev_alloc(&g->cross, g->mp_cap * g->w.np_cap));
     NNGP_TRY(dev_alloc(&g->covtmp, g->mp_cap * g->mp_cap));
-    const int64_t rows = g->mp_cap > g->np_cap ? g->mp_cap : g->np_cap;
-    if (rows > g->t_rows) {
-        dev_free(g->t);
-        NNGP_TRY(dev_alloc(&g->t, rows * NB));
-        g->t_rows = rows;
-    }
-    return 0;
+    return ws_reserve_scratch(&g->w, g->mp_cap > g->w.np_cap ? g->mp_cap : g->w.np_cap);
 }
 
 void gp_free(nngp_rbf_gp* g) {
     gp_free_test(g);
-    dev_free(g->x);
-    dev_free(g->yc);
-    dev_free(g->a);
-    dev_free(g->zt);
-    dev_free(g->ainv);
-    dev_free(g->dinv);
-    dev_free(g->wrow);
-    dev_free(g->alpha);
-    dev_free(g->part);
-    dev_free(g->red);
-    dev_free(g->status);
-    dev_free(g->t);
+    ws_free(&g->w);
 }
 
 double softplus(double x) { return x > 0.0 ? x + log1p(exp(-x)) : log1p(exp(x)); }  // logaddexp(x, 0)
@@ -401,21 +229,7 @@ int nngp_rbf_gp_create(nngp_rbf_gp** out, int64_t n_cap, int64_t m_cap, int32_t 
     *out = nullptr;
     nngp_rbf_gp* g = new (std::nothrow) nngp_rbf_gp();
     NNGP_REQUIRE(g != nullptr, "rbf_gp_create: out of host memory");
-    g->n_cap = n_cap;
-    g->d = d;
-    g->np_cap = round_up(n_cap, NB);
-    const int64_t np = g->np_cap;
-    int rc = dev_alloc(&g->x, n_cap * d);
-    if (rc == 0) rc = dev_alloc(&g->yc, np);
-    if (rc == 0) rc = dev_alloc(&g->a, np * np);
-    if (rc == 0) rc = dev_alloc(&g->zt, np * np);
-    if (rc == 0) rc = dev_alloc(&g->ainv, np * np);
-    if (rc == 0) rc = dev_alloc(&g->dinv, np * NB);
-    if (rc == 0) rc = dev_alloc(&g->wrow, NB * np);
-    if (rc == 0) rc = dev_alloc(&g->alpha, np);
-    if (rc == 0) rc = dev_alloc(&g->part, gp_nparts(n_cap) * NPART);
-    if (rc == 0) rc = dev_alloc(&g->red, 8);
-    if (rc == 0) rc = dev_alloc(&g->status, 1);
+    int rc = ws_alloc(&g->w, n_cap, d, NPART, 8, round_up(n_cap > m_cap ? n_cap : m_cap, NB));  // scratch for predict too
     if (rc == 0) rc = gp_alloc_test(g, m_cap);
     if (rc != 0) {
         gp_free(g);
@@ -438,8 +252,8 @@ int nngp_rbf_gp_set_train(nngp_rbf_gp* g, const double* x, const double* y, int6
     hipStream_t s = (hipStream_t)stream;
     NNGP_REQUIRE(g != nullptr && x != nullptr && y != nullptr, "rbf_gp_set_train: NULL argument");
     NNGP_REQUIRE(ny == 1, "rbf_gp_set_train: the GP takes one output column (ny=%d)", ny);
-    NNGP_REQUIRE(n >= 1 && n <= g->n_cap, "rbf_gp_set_train: n=%lld outside [1, n_cap=%lld]", (long long)n, (long long)g->n_cap);
-    g->have_train = g->factored = g->have_terms = false;
+    NNGP_REQUIRE(n >= 1 && n <= g->w.n_cap, "rbf_gp_set_train: n=%lld outside [1, n_cap=%lld]", (long long)n, (long long)g->w.n_cap);
+    g->have_terms = false;
     std::vector<double> h((size_t)n);
     NNGP_HIP_CHECK(hipMemcpyAsync(h.data(), y, sizeof(double) * n, hipMemcpyDeviceToHost, s));
     NNGP_HIP_CHECK(hipStreamSynchronize(s));
@@ -447,63 +261,48 @@ int nngp_rbf_gp_set_train(nngp_rbf_gp* g, const double* x, const double* y, int6
     for (int64_t i = 0; i < n; ++i) sum += h[i];
     const double mean = sum / (double)n;
     for (int64_t i = 0; i < n; ++i) h[i] -= mean;
-    g->n = n;
-    g->np = round_up(n, NB);
     g->ymean = mean;
-    NNGP_HIP_CHECK(hipMemcpyAsync(g->x, x, sizeof(double) * n * g->d, hipMemcpyDeviceToDevice, s));
-    NNGP_HIP_CHECK(hipMemsetAsync(g->yc, 0, sizeof(double) * g->np, s));
-    NNGP_HIP_CHECK(hipMemcpyAsync(g->yc, h.data(), sizeof(double) * n, hipMemcpyHostToDevice, s));
-    NNGP_HIP_CHECK(hipMemsetAsync(g->wrow, 0, sizeof(double) * NB * g->np, s));
-    NNGP_HIP_CHECK(hipStreamSynchronize(s));  // h leaves scope
-    g->have_train = true;
-    return 0;
+    return ws_set_train(&g->w, x, h.data(), hipMemcpyHostToDevice, n, s);
 }
 
 int nngp_rbf_gp_evaluate(nngp_rbf_gp* g, const double* raw, double* nlml, double* grad_raw, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     NNGP_REQUIRE(g != nullptr && raw != nullptr && nlml != nullptr, "rbf_gp_evaluate: NULL argument");
-    NNGP_REQUIRE(g->have_train, "rbf_gp_evaluate: no training data (nngp_rbf_gp_set_train)");
+    NNGP_REQUIRE(g->w.n > 0, "rbf_gp_evaluate: no training data (nngp_rbf_gp_set_train)");
     NNGP_REQUIRE(std::isfinite(raw[0]) && std::isfinite(raw[1]) && std::isfinite(raw[2]),
                  "rbf_gp_evaluate: non-finite hyperparameter (raw = %g, %g, %g)", raw[0], raw[1], raw[2]);
     const double amp = softplus(raw[0]), noise = softplus(raw[1]), ls = softplus(raw[2]);
     NNGP_REQUIRE(amp > 0.0 && ls > 0.0, "rbf_gp_evaluate: amplitude and length scale must be positive (raw = %g, %g, %g)", raw[0],
                  raw[1], raw[2]);
-    g->factored = g->have_terms = false;
-    const int64_t n = g->n, np = g->np;
+    GpWorkspace& w = g->w;
+    w.factored = g->have_terms = false;
+    const int64_t n = w.n, np = w.np;
     RbfArgs ra{};
-    ra.x1 = ra.x2 = g->x;
+    ra.x1 = ra.x2 = w.x;
     ra.n1 = ra.n2 = n;
-    ra.d = g->d;
+    ra.d = w.d;
     ra.ls = ls;
     ra.amp = amp;
     ra.diag_add = noise + 1e-6;
     ra.sym = 1;
-    ra.out = g->a;
+    ra.out = w.a;
     ra.ld = ra.rows = ra.cols = np;
     NNGP_TRY(launch_rbf(ra, s));
-    NNGP_TRY(potrf_f64(g->a, np, np, g->dinv, g->status, s));
-    NNGP_TRY(potrf_f64_status(g->status, s, "rbf_gp_evaluate"));
+    const bool grad = grad_raw != nullptr;
+    NNGP_TRY(factor_and_solve(&w, grad, "rbf_gp_evaluate", s));
     g->amp = amp;
     g->noise = noise;
     g->ls = ls;
-    NNGP_HIP_CHECK(hipMemcpyAsync(g->wrow, g->yc, sizeof(double) * np, hipMemcpyDeviceToDevice, s));
-    NNGP_TRY(trsm_fwd_f64(g->wrow, np, NB, g->a, np, g->dinv, np, g->t, false, s));
-    const bool grad = grad_raw != nullptr;
-    const int64_t nparts = gp_nparts(n);
+    const int64_t nparts = gp_lower_tiles(n);
     if (grad) {
-        hipLaunchKernelGGL(k_eye, dim3((unsigned)((np + 255) / 256), (unsigned)np), dim3(256), 0, s, g->zt, np, np);
-        NNGP_HIP_CHECK(hipGetLastError());
-        NNGP_TRY(trsm_fwd_f64(g->zt, np, np, g->a, np, g->dinv, np, g->t, true, s));
-        NNGP_TRY(launch_gemm_nt_f64(g->ainv, np, nullptr, 0, g->zt, np, g->zt, np, np, np, np, 1.0, 0.0, s));
-        hipLaunchKernelGGL(k_rowdot, dim3((unsigned)np), dim3(256), 0, s, g->zt, np, np, g->wrow, g->alpha, 0.0, nullptr, 0.0);
-        hipLaunchKernelGGL(k_gp_grad_partial, dim3((unsigned)nparts), dim3(256), 0, s, g->x, n, g->d, ls, g->ainv, np, g->alpha, g->part);
+        hipLaunchKernelGGL(k_gp_grad_partial, dim3((unsigned)nparts), dim3(256), 0, s, w.x, n, w.d, ls, w.ainv, np, w.alpha, w.part);
         NNGP_HIP_CHECK(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_gp_finish, dim3(1), dim3(256), 0, s, g->a, np, n, g->wrow, grad ? g->part : nullptr, nparts,
-                       grad ? g->alpha : nullptr, g->ainv, g->red);
+    hipLaunchKernelGGL(k_gp_finish, dim3(1), dim3(256), 0, s, w.a, np, n, w.wrow, grad ? w.part : nullptr, nparts,
+                       grad ? w.alpha : nullptr, w.ainv, w.red);
     NNGP_HIP_CHECK(hipGetLastError());
     double r[8];
-    NNGP_HIP_CHECK(hipMemcpyAsync(r, g->red, sizeof(r), hipMemcpyDeviceToHost, s));
+    NNGP_HIP_CHECK(hipMemcpyAsync(r, w.red, sizeof(r), hipMemcpyDeviceToHost, s));
     NNGP_HIP_CHECK(hipStreamSynchronize(s));
     const double c = log(2.0 * 3.1415);
     const double la = log(amp);
@@ -515,10 +314,10 @@ int nngp_rbf_gp_evaluate(nngp_rbf_gp* g, const double* raw, double* nlml, double
         grad_raw[0] = g_amp * sigmoid(raw[0]);
         grad_raw[1] = g_noise * sigmoid(raw[1]);
         grad_raw[2] = g_ls * sigmoid(raw[2]);
+        for (int i = 0; i < 8; ++i) g->terms[i] = r[i];
         g->have_terms = true;
     }
-    for (int i = 0; i < 8; ++i) g->terms[i] = r[i];
-    g->factored = true;
+    w.factored = true;
     return 0;
 }
 
@@ -536,18 +335,18 @@ int nngp_rbf_gp_predict(nngp_rbf_gp* g, const double* x_test, int64_t mt, int32_
     NNGP_REQUIRE(cov_mode == NNGP_COV_NONE || cov_mode == NNGP_COV_DIAG || cov_mode == NNGP_COV_FULL, "rbf_gp_predict: bad cov_mode %d",
                  cov_mode);
     NNGP_REQUIRE(cov_mode == NNGP_COV_NONE || var_or_cov != nullptr, "rbf_gp_predict: NULL covariance output");
-    NNGP_REQUIRE(g->factored, "rbf_gp_predict: no successful nngp_rbf_gp_evaluate since the training data was set");
+    NNGP_REQUIRE(g->w.factored, "rbf_gp_predict: no successful nngp_rbf_gp_evaluate since the training data was set");
     if (mt > g->m_cap) {  // the only allocation after create
         NNGP_HIP_CHECK(hipStreamSynchronize(s));
         NNGP_TRY(gp_alloc_test(g, mt));
     }
-    const int64_t np = g->np, mp = round_up(mt, NB);
+    const int64_t np = g->w.np, mp = round_up(mt, NB);
     RbfArgs ra{};
     ra.x1 = x_test;
-    ra.x2 = g->x;
+    ra.x2 = g->w.x;
     ra.n1 = mt;
-    ra.n2 = g->n;
-    ra.d = g->d;
+    ra.n2 = g->w.n;
+    ra.d = g->w.d;
     ra.ls = g->ls;
     ra.amp = g->amp;
     ra.out = g->cross;
@@ -555,9 +354,9 @@ int nngp_rbf_gp_predict(nngp_rbf_gp* g, const double* x_test, int64_t mt, int32_
     ra.rows = mp;
     ra.cols = np;
     NNGP_TRY(launch_rbf(ra, s));
-    NNGP_TRY(trsm_fwd_f64(g->cross, np, mp, g->a, np, g->dinv, np, g->t, false, s));  // V^T = amp K(X_t, X) L^-T
+    NNGP_TRY(trsm_fwd_f64(g->cross, np, mp, g->w.a, np, g->w.dinv, np, g->w.t, false, s));  // V^T = amp K(X_t, X) L^-T
     // mean = V^T w + mean(y)  (= amp K(X_t, X) alpha + mean(y));  var = amp - |V^T row|^2
-    hipLaunchKernelGGL(k_rowdot, dim3((unsigned)mt), dim3(256), 0, s, g->cross, np, np, g->wrow, mean, g->ymean,
+    hipLaunchKernelGGL(k_rowdot, dim3((unsigned)mt), dim3(256), 0, s, g->cross, np, np, g->w.wrow, mean, g->ymean,
                        cov_mode == NNGP_COV_DIAG ? var_or_cov : nullptr, g->amp);
     NNGP_HIP_CHECK(hipGetLastError());
     if (cov_mode == NNGP_COV_FULL) {
@@ -565,7 +364,7 @@ int nngp_rbf_gp_predict(nngp_rbf_gp* g, const double* x_test, int64_t mt, int32_
         RbfArgs rc{};
         rc.x1 = rc.x2 = x_test;
         rc.n1 = rc.n2 = mt;
-        rc.d = g->d;
+        rc.d = g->w.d;
         rc.ls = g->ls;
         rc.amp = g->amp;
         rc.out = var_or_cov;
@@ -597,10 +396,10 @@ int nngp_rbf_gp_kernel(const double* x1, int64_t n1, const double* x2, int64_t n
 
 int nngp_rbf_gp_factor_buffer(const nngp_rbf_gp* g, double** l, int64_t* ld, int64_t* n_padded) {
     NNGP_REQUIRE(g != nullptr && l != nullptr && ld != nullptr, "rbf_gp_factor_buffer: NULL argument");
-    NNGP_REQUIRE(g->factored, "rbf_gp_factor_buffer: no factor (nngp_rbf_gp_evaluate)");
-    *l = g->a;
-    *ld = g->np;
-    if (n_padded) *n_padded = g->np;
+    NNGP_REQUIRE(g->w.factored, "rbf_gp_factor_buffer: no factor (nngp_rbf_gp_evaluate)");
+    *l = g->w.a;
+    *ld = g->w.np;
+    if (n_padded) *n_padded = g->w.np;
     return 0;
 }
 

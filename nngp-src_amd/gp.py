@@ -52,22 +52,29 @@ def train_hyperparameters(evaluate, raw0=RAW0, steps=STEPS, lr=LR, report=print)
     return raw, history
 
 
-class RBFGP:
-    """Handle of one float64 RBF GP on the GPU (nngp_rbf_gp_*).  Inputs are numpy or torch arrays; outputs numpy."""
+class F64Handle:
+    """create / close / set_train / factor of a float64 evidence handle on the GPU (``<prefix>create`` ... of the C ABI: the RBF
+    GP's ``nngp_rbf_gp_`` and the NNGP marginal likelihood's ``nngp_mll_``).  Inputs are numpy or torch arrays; outputs numpy."""
 
-    def __init__(self, n_cap: int, d: int, m_cap: int = 0):
-        import torch
-        self._torch = torch
+    _prefix = None
+
+    def __init__(self, d: int, *create_args):
         self.lib = _lib.load()
         self.device = _lib.require_gpu()
         self.d = int(d)
         self._h = ctypes.c_void_p()
-        _lib.check(self.lib.nngp_rbf_gp_create(ctypes.byref(self._h), int(n_cap), int(m_cap), self.d), self.lib)
+        self._check(self._fn("create")(ctypes.byref(self._h), *create_args))
         self.n = 0
+
+    def _fn(self, name):
+        return getattr(self.lib, self._prefix + name)
+
+    def _check(self, rc):
+        _lib.check(rc, self.lib)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
-            self.lib.nngp_rbf_gp_destroy(self._h)
+            self._fn("destroy")(self._h)
             self._h = None
 
     def __del__(self):
@@ -76,18 +83,34 @@ class RBFGP:
         except Exception:
             pass
 
-    def _check(self, rc):
-        _lib.check(rc, self.lib)
-
     def set_train(self, x, y):
         xd = _lib.to_device_f64(x, self.device)
         yd = _lib.to_device_f64(y, self.device)
         if xd.dim() != 2 or xd.shape[1] != self.d:
             raise ValueError("x must be [n, %d]" % self.d)
         ny = 1 if yd.dim() == 1 else yd.shape[1]
-        self._check(self.lib.nngp_rbf_gp_set_train(self._h, _lib.ptr(xd), _lib.ptr(yd), xd.shape[0], ny, _lib.stream_ptr()))
+        self._check(self._fn("set_train")(self._h, _lib.ptr(xd), _lib.ptr(yd), xd.shape[0], ny, _lib.stream_ptr()))
         self.n = xd.shape[0]
         return self
+
+    def factor(self):
+        """The device factor of the last evaluation as a zero-copy torch view [n_padded, ld] (read its lower triangle;
+        valid until the next evaluation or close)."""
+        from .model import _wrap_device
+        p, ld, npad = ctypes.c_void_p(), ctypes.c_int64(), ctypes.c_int64()
+        self._check(self._fn("factor_buffer")(self._h, ctypes.byref(p), ctypes.byref(ld), ctypes.byref(npad)))
+        return _wrap_device(p.value, npad.value * ld.value, self.device, "<f8").view(npad.value, ld.value)
+
+
+class RBFGP(F64Handle):
+    """Handle of one float64 RBF GP on the GPU (nngp_rbf_gp_*)."""
+
+    _prefix = "nngp_rbf_gp_"
+
+    def __init__(self, n_cap: int, d: int, m_cap: int = 0):
+        import torch
+        self._torch = torch
+        super().__init__(d, int(n_cap), int(m_cap), int(d))
 
     def evaluate(self, raw, with_grad: bool = True):
         """NLML (and its gradient with respect to the raw parameters) at ``raw`` = (amplitude, noise, lengthscale)."""
@@ -119,14 +142,6 @@ class RBFGP:
         self._check(self.lib.nngp_rbf_gp_predict(self._h, _lib.ptr(xt), mt, mode, _lib.ptr(mean), _lib.ptr(out), _lib.stream_ptr()))
         torch.cuda.current_stream().synchronize()
         return mean.cpu().numpy().reshape(mt, 1), (None if out is None else out.cpu().numpy())
-
-    def factor(self):
-        """The device factor of the last evaluation as a zero-copy torch view [n_padded, ld] (read its lower triangle;
-        valid until the next evaluation or close)."""
-        from .model import _wrap_device
-        p, ld, npad = ctypes.c_void_p(), ctypes.c_int64(), ctypes.c_int64()
-        self._check(self.lib.nngp_rbf_gp_factor_buffer(self._h, ctypes.byref(p), ctypes.byref(ld), ctypes.byref(npad)))
-        return _wrap_device(p.value, npad.value * ld.value, self.device, "<f8").view(npad.value, ld.value)
 
 
 def kernel(x1, x2, ls):

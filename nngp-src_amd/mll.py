@@ -20,7 +20,7 @@ import math
 import numpy as np
 
 from . import _lib, stax
-from .gp import train_hyperparameters
+from .gp import F64Handle, train_hyperparameters
 
 
 def _arch_of(kernel_fn_or_params):
@@ -50,39 +50,14 @@ def check_supported(kernel_fn_or_params, get="nngp"):
     return w, b, acts
 
 
-class NNGPMarginalLikelihood:
-    """Handle of one float64 NNGP evidence evaluator on the GPU (nngp_mll_*).  Inputs numpy or torch; outputs numpy."""
+class NNGPMarginalLikelihood(F64Handle):
+    """Handle of one float64 NNGP evidence evaluator on the GPU (nngp_mll_*)."""
+
+    _prefix = "nngp_mll_"
 
     def __init__(self, n_cap: int, d: int):
-        self.lib = _lib.load()
-        self.device = _lib.require_gpu()
-        self.d = int(d)
-        self._h = ctypes.c_void_p()
-        _lib.check(self.lib.nngp_mll_create(ctypes.byref(self._h), int(n_cap), self.d), self.lib)
-        self.n = 0
+        super().__init__(d, int(n_cap), int(d))
         self.n_dense = 0
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self.lib.nngp_mll_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_train(self, x, y):
-        xd = _lib.to_device_f64(x, self.device)
-        yd = _lib.to_device_f64(y, self.device)
-        if xd.dim() != 2 or xd.shape[1] != self.d:
-            raise ValueError("x must be [n, %d]" % self.d)
-        ny = 1 if yd.dim() == 1 else yd.shape[1]
-        _lib.check(self.lib.nngp_mll_set_train(self._h, _lib.ptr(xd), _lib.ptr(yd), xd.shape[0], ny, _lib.stream_ptr()),
-                   self.lib)
-        self.n = xd.shape[0]
-        return self
 
     def evaluate(self, kernel_fn_or_params, diag_reg=1e-3, absolute=False, with_grad=True):
         """(nlml, grad) at the architecture of ``kernel_fn_or_params``.  grad (numpy, 2 n_dense + 1 values): d/dsigma_w,l^2,
@@ -91,8 +66,8 @@ class NNGPMarginalLikelihood:
         arch = _lib.make_arch_act(w, b, acts)
         nlml = ctypes.c_double()
         g = (ctypes.c_double * (2 * len(w) + 1))()
-        _lib.check(self.lib.nngp_mll_evaluate(self._h, ctypes.byref(arch), float(diag_reg), int(bool(absolute)),
-                                              ctypes.byref(nlml), g if with_grad else None, _lib.stream_ptr()), self.lib)
+        self._check(self.lib.nngp_mll_evaluate(self._h, ctypes.byref(arch), float(diag_reg), int(bool(absolute)),
+                                               ctypes.byref(nlml), g if with_grad else None, _lib.stream_ptr()))
         self.n_dense = len(w)
         return nlml.value, (np.array(g[:], dtype=np.float64) if with_grad else None)
 
@@ -102,18 +77,11 @@ class NNGPMarginalLikelihood:
         nc = 2 * self.n_dense
         count = 2 * (nc + 1) + 5 + nc
         out = (ctypes.c_double * count)()
-        _lib.check(self.lib.nngp_mll_terms(self._h, out, count), self.lib)
+        self._check(self.lib.nngp_mll_terms(self._h, out, count))
         v = np.array(out[:], dtype=np.float64)
         t = v[2 * (nc + 1):]
         return {"quad": v[0:2 * (nc + 1):2], "trace": v[1:2 * (nc + 1):2], "logdet_half": t[0], "y_ainv_y": t[1],
                 "tr_k": t[2], "a_a": t[3], "tr_ainv": t[4], "tr_dk": t[5:5 + nc]}
-
-    def factor(self):
-        """The device factor of the last evaluation as a zero-copy torch view [n_padded, ld] (read its lower triangle)."""
-        from .model import _wrap_device
-        p, ld, npad = ctypes.c_void_p(), ctypes.c_int64(), ctypes.c_int64()
-        _lib.check(self.lib.nngp_mll_factor_buffer(self._h, ctypes.byref(p), ctypes.byref(ld), ctypes.byref(npad)), self.lib)
-        return _wrap_device(p.value, npad.value * ld.value, self.device, "<f8").view(npad.value, ld.value)
 
 
 def _grad_dict(g, n_dense):
