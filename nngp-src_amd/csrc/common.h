@@ -43,7 +43,7 @@ void note_alloc();  // counts a device allocation (nngp_alloc_count)
 //      61 = the factor's inverted blocks built in line (not beside the first predict's cross-kernel build); 62 = digit planes of K row by row; 63 = per-layer ReLU recursion in the kernel build (no composite map); 64 = seven z planes in FINE products; 65 = an NTK model's NNGP kernel always in a build of its own
 //   0  (also) 32 = alpha CG runs in stream order inside nngp_model_solve, early-stopped (resumed by whoever needs alpha itself)
 //   8  round 4, grouped Cholesky (set BEFORE the model is created): bit 1 = the schedule with the panel solves off the update stream
-//      (potrf_lookahead_grouped_v4; needs its extra streams); with it: 2 = bulk panel solves on the panel stream itself; 4 = early part
+//      (potrf_lookahead.hip, potrf_lookahead_grouped_v4; needs its extra streams); with it: 2 = bulk panel solves on the panel stream itself; 4 = early part
 //      of the next group's first diagonal-block update on its own stream; 8 = helper grids behind the bulk solves; 16 = a far chunk's
 //      next-column region in a launch of its own; 32 = finished diagonal blocks inverted on a side stream under the last block columns
 //   9  round 4, posterior solves: 2 = 2048-wide inverted blocks / two 1024-column panels per step of the blocked solves from np = 8192 on
@@ -157,7 +157,10 @@ int launch_gemm_nt_h3x(float* c, int64_t ldc, const char* a, const char* b, int6
 // ---- potrf.hip ----
 int launch_potrf_leaf(float* a, int64_t ld, float* dinv_block, int32_t* clamped, float pivot_floor, hipStream_t s);
 int potrf_f32(float* a, int64_t n, int64_t ld, float* dinv, int32_t* clamped, float pivot_floor, hipStream_t s);
+int potrf_rec(float* a, int64_t n, int64_t ld, float* dinv, int32_t* clamped, float pivot_floor, hipStream_t s);  // potrf_f32 without its argument checks
 int trsm_rlt_f32(float* b, int64_t ldb, int64_t m, const float* l, int64_t ldl, const float* dinv, int64_t n,
+                 hipStream_t s);
+int trsm_rut_f32(float* b, int64_t ldb, int64_t m, const float* lt, int64_t ldl, const float* dinvt, int64_t n,
                  hipStream_t s);
 
 // ---- trsm_panel.hip: b [m, w] <- b L^-T in one launch (w <= 1024), optionally with the rows' float16 split copy ----
@@ -226,21 +229,20 @@ struct LookAhead {  // streams and events of the look-ahead Cholesky (one per mo
     double tu_flops[kMaxTimed] = {};
     double tu_bytes[kMaxTimed] = {};  // algorithmic bytes: C read + written once (8 B per updated entry) + the split rows of the operands once
 };
+// ---- potrf_lookahead.hip: the look-ahead schedules and the block-column ABI of the multi-GPU factorisation (host code only) ----
 int lookahead_create(LookAhead** out);
 void lookahead_destroy(LookAhead* la);
 struct TriInv;
 int potrf_lookahead_f32(float* a, int64_t n, int64_t ld, float* dinv, int32_t* clamped, float pivot_floor,
                         LookAhead* la, SplitWork* sw, hipStream_t user, TriInv* ti = nullptr);  // ti: invert finished diagonal blocks on the way
 constexpr int64_t kLookAheadNb = 1024;  // block-column width of the look-ahead Cholesky
-constexpr int kLookAheadGroup = 4;      // block columns per deep-K far update (potrf.hip, grouped form)
+constexpr int kLookAheadGroup = 4;      // block columns per deep-K far update (potrf_lookahead.hip, grouped form)
 int potrf_panel_f32(float* a, int64_t n, int64_t ld, float* dinv, int32_t* clamped, float pivot_floor, int64_t o,
                     int64_t w, hipStream_t s, SplitWork* sw = nullptr);
 int potrf_update_f32(float* a, int64_t n, int64_t ld, int64_t po, int64_t pw, int64_t o, int64_t w, hipStream_t s,
                      SplitWork* sw = nullptr);  // sw: run the update on the float16 pipe (split copy of the panel kept in sw)
 int potrf_update_cols_f32(float* a, int64_t n, int64_t ld, int64_t po, int64_t pw, const int64_t* cols, int ncols, int64_t w,
                           hipStream_t s, SplitWork* sw = nullptr);  // several target block columns, four to a split-float16 launch
-int trsm_rut_f32(float* b, int64_t ldb, int64_t m, const float* lt, int64_t ldl, const float* dinvt, int64_t n,
-                 hipStream_t s);
 
 // ---- gemm_i8s.hip: float64-grade products on the int8 matrix pipe (exactly sliced operands) ----
 struct I8Plan {       // which digit-plane pairs are multiplied, grouped by diagonal ia + ib (largest first)

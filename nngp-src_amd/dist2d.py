@@ -325,7 +325,7 @@ class Dist2DGP:
             if mr > 0 and mc > 0:  # ONE update of the local trailing tiles (upper ones included: never read)
                 # on the float16 pipe from the second block column on, when the local tiles fill the GPU (>= 96 tiles of 256 x 256,
                 # as in the single-GPU solves); block column 0 -- the kernel's dominant, one-signed columns -- stays float32
-                # (accumulator truncation of the float16 pipe on same-sign sums: potrf.hip)
+                # (accumulator truncation of the float16 pipe on same-sign sums: potrf_lookahead.hip, kLeadF32Cols)
                 h3 = getattr(ops, "gemm_nt_h3", None)
                 # (h3_scale assumes |L_ij| <= sqrt(max A_ii); after a clamped pivot entries can exceed that and the float16 planes would
                 # overflow to inf: from then on this rank's updates stay float32, so that the factor is finite and `clamped` can report it)

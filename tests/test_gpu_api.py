@@ -371,7 +371,7 @@ def test_checkpoint_save_and_resume(tmp_path):
 
 def test_update_timer_reports_the_trailing_update_launches():
     """bench.py's `roofline` is measured live: nngp_model_update_timer puts HIP events around every split-float16 update launch
-    of the factorisation.  N = 5120 = 5 block columns, grouped form with 4 columns per group (potrf.hip): block columns 0..2 are
+    of the factorisation.  N = 5120 = 5 block columns, grouped form with 4 columns per group (potrf_lookahead.hip): block columns 0..2 are
     applied to the rest of their group at once -- rows below the next diagonal block x the group's remaining columns, on or below
     the diagonal (the diagonal blocks themselves are float32 GEMMs) -- so three launches; the group's far update has only the
     last diagonal block to reach, which is a float32 GEMM too.  Their algorithmic work is 2 x entries x (panel width; the first

@@ -404,7 +404,7 @@ def test_grouped_cholesky_matches_the_one_column_form(n):
 @pytest.mark.parametrize("n", [9300, 13440])
 def test_cholesky_schedule_with_the_panel_solves_off_the_update_stream(n):
     """Round 4's experimental schedule of the grouped Cholesky (debug key 8 bit 1, knobs build only: panel solves on the panel / bulk
-    streams, trailing updates alone on the update stream -- measured no faster than round 3's, see potrf.hip) against the product's
+    streams, trailing updates alone on the update stream -- measured no faster than round 3's, see potrf_lookahead.hip) against the product's
     schedule.  Every tile sees the same arithmetic in the same order: the factors, alpha and the posterior of a block of queries
     must agree BIT FOR BIT -- any read-modify-write race between the streams would show here.  Also with a far chunk's next-column
     region in its own launch (16) and the finished diagonal blocks inverted on a side stream under the last block columns (32).
