@@ -28,6 +28,50 @@ def kernel_build(x1, x2, w_std, b_std, get=("nngp", "ntk"), rows=None, dtype=tor
     return {g: t.cpu().numpy() for g, t in outs.items()}
 
 
+def build_act(x1, x2, w_std, b_std, acts, get=("nngp", "ntk"), rows=None, dtype=torch.float64, ld=None):
+    """kernel_build for a network with other activations (nngp_kernel_build_act)."""
+    lib = _lib.load()
+    x1d = _lib.to_device_f64(x1, dev())
+    x2d = None if x2 is None else _lib.to_device_f64(x2, dev())
+    n1, d = x1d.shape
+    n2 = n1 if x2d is None else x2d.shape[0]
+    ld = n2 if ld is None else ld
+    outs = {g: torch.full((n1, ld), float("nan"), dtype=dtype, device=dev()) for g in get}
+    arch = _lib.make_arch_act(w_std, b_std, acts)
+    r0, r1 = (0, n1) if rows is None else rows
+    _lib.check(lib.nngp_kernel_build_act(_lib.ptr(x1d), n1, _lib.ptr(x2d), n2, d, ctypes.byref(arch),
+                                         _lib.DTYPE_F64 if dtype == torch.float64 else _lib.DTYPE_F32,
+                                         _lib.ptr(outs.get("nngp")), _lib.ptr(outs.get("ntk")), ld, r0, r1, _lib.stream_ptr()))
+    torch.cuda.synchronize()
+    return {g: t.cpu().numpy() for g, t in outs.items()}
+
+
+def diag_act(x, w_std, b_std, acts):
+    """(K(x, x), Theta(x, x)) per row through nngp_kernel_diag_act."""
+    lib = _lib.load()
+    xd = _lib.to_device_f64(x, dev())
+    dn = torch.empty(xd.shape[0], dtype=torch.float64, device=dev())
+    dt = torch.empty_like(dn)
+    arch = _lib.make_arch_act(w_std, b_std, acts)
+    _lib.check(lib.nngp_kernel_diag_act(_lib.ptr(xd), xd.shape[0], xd.shape[1], ctypes.byref(arch), _lib.ptr(dn), _lib.ptr(dt),
+                                        _lib.stream_ptr()))
+    torch.cuda.synchronize()
+    return dn.cpu().numpy(), dt.cpu().numpy()
+
+
+def kernel_diag(x, w_std, b_std):
+    """(K(x, x), Theta(x, x)) per row through nngp_kernel_diag (all-ReLU network)."""
+    lib = _lib.load()
+    xd = _lib.to_device_f64(x, dev())
+    dn = torch.empty(xd.shape[0], dtype=torch.float64, device=dev())
+    dt = torch.empty_like(dn)
+    arch = _lib.make_arch(w_std, b_std)
+    _lib.check(lib.nngp_kernel_diag(_lib.ptr(xd), xd.shape[0], xd.shape[1], ctypes.byref(arch), _lib.ptr(dn), _lib.ptr(dt),
+                                    _lib.stream_ptr()))
+    torch.cuda.synchronize()
+    return dn.cpu().numpy(), dt.cpu().numpy()
+
+
 def gemm_nt(c, a, b, alpha, beta, lower_only=False):
     lib = _lib.load()
     m, k = a.shape

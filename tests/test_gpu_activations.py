@@ -31,33 +31,7 @@ def _arch(acts, w=1.1, b=0.0):
     return [w] * nd, [b] * nd, list(acts)
 
 
-def build_act(x1, x2, w_std, b_std, acts, get=("nngp", "ntk"), rows=None, dtype=torch.float64, ld=None):
-    lib = _lib.load()
-    x1d = _lib.to_device_f64(x1, G.dev())
-    x2d = None if x2 is None else _lib.to_device_f64(x2, G.dev())
-    n1, d = x1d.shape
-    n2 = n1 if x2d is None else x2d.shape[0]
-    ld = n2 if ld is None else ld
-    outs = {g: torch.full((n1, ld), float("nan"), dtype=dtype, device=G.dev()) for g in get}
-    arch = _lib.make_arch_act(w_std, b_std, acts)
-    r0, r1 = (0, n1) if rows is None else rows
-    _lib.check(lib.nngp_kernel_build_act(_lib.ptr(x1d), n1, _lib.ptr(x2d), n2, d, ctypes.byref(arch),
-                                         _lib.DTYPE_F64 if dtype == torch.float64 else _lib.DTYPE_F32,
-                                         _lib.ptr(outs.get("nngp")), _lib.ptr(outs.get("ntk")), ld, r0, r1, _lib.stream_ptr()))
-    torch.cuda.synchronize()
-    return {g: t.cpu().numpy() for g, t in outs.items()}
-
-
-def diag_act(x, w_std, b_std, acts):
-    lib = _lib.load()
-    xd = _lib.to_device_f64(x, G.dev())
-    dn = torch.empty(xd.shape[0], dtype=torch.float64, device=G.dev())
-    dt = torch.empty_like(dn)
-    arch = _lib.make_arch_act(w_std, b_std, acts)
-    _lib.check(lib.nngp_kernel_diag_act(_lib.ptr(xd), xd.shape[0], xd.shape[1], ctypes.byref(arch), _lib.ptr(dn), _lib.ptr(dt),
-                                        _lib.stream_ptr()))
-    torch.cuda.synchronize()
-    return dn.cpu().numpy(), dt.cpu().numpy()
+build_act, diag_act = G.build_act, G.diag_act  # (shared with test_gpu_kernel_angles.py)
 
 
 def _close(got, want, tol=1e-11, x1=None, x2=None):

@@ -31,6 +31,9 @@ def _rows(golden_dir, kind, n):
     f = _forest(golden_dir)
     x = np.concatenate([f["X_train"], f["X_test"]] * 5)[:n]
     y = np.concatenate([f["Y_train"], f["Y_test"]] * 5)[:n].reshape(-1)
+    if kind == "centred":  # obtuse angles and mixed signs: the other half of the arctangent's table, in the adjoint pass too
+        x = x / 1000.0
+        return x - x.mean(0), y
     return (x / 1000.0 if kind == "unit" else x), y
 
 
@@ -63,6 +66,8 @@ CASES = [  # n, n_dense, W_std, b_std, absolute, rows
     (4097, 2, 1.0, 0.05, False, "unit"),
     (4097, 4, 1.5, 0.0, False, "raw"),
     (4097, 4, 1.0, 0.05, True, "synthetic"),
+    (1000, 2, 1.0, 0.0, False, "centred"),
+    (1000, 4, 1.5, 0.05, False, "centred"),
 ]
 
 

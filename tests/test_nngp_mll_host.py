@@ -88,8 +88,24 @@ def test_oracle_gradient_against_torch_autograd(net, absolute):
 @pytest.mark.parametrize("absolute", [False, True])
 @pytest.mark.parametrize("net", range(len(NETS)))
 def test_oracle_gradient_against_central_differences(net, absolute):
-    w, b, acts = NETS[net]
     x, y = _data(seed=1)
+    _central_differences(x, y, net, absolute)
+
+
+def test_oracle_gradient_against_central_differences_on_centred_forest_rows(golden_dir):
+    """The rows of the GPU file's "centred" cases (unit forest rows minus their mean: obtuse angles, mixed signs), so that the
+    oracle is itself checked at the angles it is about to referee."""
+    g = np.load(os.path.join(golden_dir, "forest_n1000_m200.npz"))
+    x = g["X_train"][:90] / 1000.0
+    x = x - x.mean(0)
+    y = g["Y_train"][:90].reshape(-1)
+    cos = (x @ x.T) / np.sqrt(np.outer((x * x).sum(1), (x * x).sum(1)))
+    assert cos.min() < -0.5 and (cos < 0).mean() > 0.3
+    _central_differences(x, y, 1, False)
+
+
+def _central_differences(x, y, net, absolute):
+    w, b, acts = NETS[net]
     v, c = R.variances(w, b)
     lam = 1e-3 if not absolute else 0.05
     o = R.Oracle(x, y, block=40)
