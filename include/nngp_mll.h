@@ -32,7 +32,7 @@ extern "C" {
 /* Everything is float64 and has its own factorisation (the float64 Cholesky behind nngp_potrf_f64); the NNGP model is not
  * involved.  The handle holds A / L, L^-T and A^-1 (3 Np^2 doubles, Np = n_cap rounded up to 128), the row norms, y,
  * alpha, w = L^-1 y and the gradient partials.  No device allocation after create.  One handle is driven from one stream
- * at a time. */
+ * at a time.  The same handle serves the leave-one-out objectives of nngp_loo.h. */
 typedef struct nngp_mll nngp_mll;
 int nngp_mll_create(nngp_mll** out, int64_t n_cap, int32_t d);
 int nngp_mll_destroy(nngp_mll* h);
@@ -50,7 +50,8 @@ int nngp_mll_evaluate(nngp_mll* h, const nngp_arch_act* arch, double diag_reg, i
  * 2 (2 n_dense + 1) + 5 + 2 n_dense). */
 int nngp_mll_terms(const nngp_mll* h, double* out, int32_t count);
 /* Device factor of the last evaluation: L in the lower triangle of [n_padded, ld] (identity on the padding; the part above
- * the diagonal blocks is workspace, read the lower triangle only). */
+ * the diagonal blocks is workspace, read the lower triangle only).  An error after a leave-one-out evaluation with a
+ * gradient (nngp_loo.h), which reuses the factor's storage. */
 int nngp_mll_factor_buffer(const nngp_mll* h, double** l, int64_t* ld, int64_t* n_padded);
 
 #ifdef __cplusplus

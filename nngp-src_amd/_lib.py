@@ -50,6 +50,11 @@ MLL_ABI_SYMBOLS = ("nngp_mll_create", "nngp_mll_destroy", "nngp_mll_set_train", 
                    "nngp_mll_factor_buffer")
 
 
+# include/nngp_loo.h: leave-one-out cross-validation on the nngp_mll handle; GPU library only (no host build)
+LOO_ABI_SYMBOLS = ("nngp_mll_loo_evaluate", "nngp_mll_loo_predictions", "nngp_mll_loo_terms")
+LOO_NLPD, LOO_MSE = 0, 1
+
+
 class NngpArch(ctypes.Structure):
     _fields_ = [("n_dense", ctypes.c_int32), ("reserved", ctypes.c_int32),
                 ("w_std", ctypes.c_double * MAX_DENSE), ("b_std", ctypes.c_double * MAX_DENSE)]
@@ -96,6 +101,7 @@ def load(knobs: bool = False):
     bind_gp_prototypes(lib)
     bind_act_prototypes(lib)
     bind_mll_prototypes(lib)
+    bind_loo_prototypes(lib)
     _libs[knobs] = lib
     return lib
 
@@ -220,6 +226,18 @@ def bind_mll_prototypes(lib):
     lib.nngp_mll_terms.argtypes = [vp, ctypes.POINTER(dbl), i32]
     lib.nngp_mll_factor_buffer.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(i64), ctypes.POINTER(i64)]
     for name in MLL_ABI_SYMBOLS:
+        getattr(lib, name).restype = ctypes.c_int
+    return lib
+
+
+def bind_loo_prototypes(lib):
+    """Argument and result types of include/nngp_loo.h (the HIP library only)."""
+    vp, i32, dbl = ctypes.c_void_p, ctypes.c_int32, ctypes.c_double
+    lib.nngp_mll_loo_evaluate.argtypes = [vp, ctypes.POINTER(NngpArchAct), i32, dbl, i32, i32, ctypes.POINTER(dbl),
+                                          ctypes.POINTER(dbl), vp]
+    lib.nngp_mll_loo_predictions.argtypes = [vp, vp, vp, vp]
+    lib.nngp_mll_loo_terms.argtypes = [vp, ctypes.POINTER(dbl), i32]
+    for name in LOO_ABI_SYMBOLS:
         getattr(lib, name).restype = ctypes.c_int
     return lib
 

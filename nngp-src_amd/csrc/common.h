@@ -50,6 +50,7 @@ void note_alloc();  // counts a device allocation (nngp_alloc_count)
 //      (measured: posterior -0.5 ms, block inverses +1.1 ms at N = 32768 -- off)
 //  10  block columns from the end where key 8 = 32 issues the inverses; 11  priority of that side stream; 12  print the schedule's stream end times
 //  13  compute units the posterior solves' update grids leave to the alpha CG; 14  2 = CG iterations replayed from a hipGraph
+//  15  1 = leave-one-out gradient: C = A^-1 diag(bbar) A^-1 as one square product instead of row panels up to the diagonal (nngp_loo.hip)
 #ifdef NNGP_TIMING_KNOBS
 extern std::atomic<int> g_knobs[16];
 #define NNGP_KNOB(i) (nngp::g_knobs[i].load(std::memory_order_relaxed))

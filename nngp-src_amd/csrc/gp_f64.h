@@ -49,8 +49,11 @@ int ws_reserve_scratch(GpWorkspace* w, int64_t rows);  // grows t to at least ro
 void ws_free(GpWorkspace* w);
 // x: device [n, d]; y: n values, device or host by y_kind, zero padded to Np; zeroes wrow and synchronises
 int ws_set_train(GpWorkspace* w, const double* x, const double* y, hipMemcpyKind y_kind, int64_t n, hipStream_t s);
-// L = chol(A) in place (A filled by the caller), w = L^-1 y; with_inverse: also L^-T, A^-1 and alpha.  who prefixes the error.
-int factor_and_solve(GpWorkspace* w, bool with_inverse, const char* who, hipStream_t s);
+// L = chol(A) in place (A filled by the caller), w = L^-1 y; kGpSolveInverse (what `true` converts to): also L^-T, A^-1 and
+// alpha; kGpSolveRows: L^-T and alpha without the A^-1 product.  neg_rowsq [Np]: minus the row sums of squares of L^-T, that is
+// -[A^-1]_ii, from the pass that forms alpha (alpha's bits do not depend on it).  who prefixes the error.
+enum { kGpSolveW = 0, kGpSolveInverse = 1, kGpSolveRows = 2 };
+int factor_and_solve(GpWorkspace* w, int mode, const char* who, hipStream_t s, double* neg_rowsq = nullptr);
 
 // Workgroup b runs on XCD b % 8: deal each XCD a contiguous range of the tile order, so that neighbouring tiles (which share
 // row panels of X) meet in one L2 -- the ordering of gemm_f64.hip / kernel_build.hip.

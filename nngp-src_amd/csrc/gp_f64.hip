@@ -6,7 +6,8 @@
 //   potrf_f64         blocked right-looking Cholesky: k_chol_diag, then the panel L21 = A21 L11^-T and the trailing update
 //                     A22 -= L21 L21^T on the float64 MFMA GEMM (gemm_f64.hip)
 //   trsm_fwd_f64      B^T <- B^T L^-T (each row b of B^T becomes L^-1 b), left-looking by 128-column blocks, two GEMMs per block
-//   factor_and_solve  potrf_f64, w = L^-1 y and, for a gradient, L^-T (trsm_fwd_f64 on the identity), A^-1 = L^-T L^-1 and alpha
+//   factor_and_solve  potrf_f64, w = L^-1 y and, for a gradient, L^-T (trsm_fwd_f64 on the identity), A^-1 = L^-T L^-1 and alpha;
+//                     kGpSolveRows stops short of the A^-1 product (the leave-one-out values need only the rows of L^-T)
 #include "gp_f64.h"
 
 namespace nngp {
@@ -189,18 +190,18 @@ int ws_set_train(GpWorkspace* w, const double* x, const double* y, hipMemcpyKind
     return 0;
 }
 
-int factor_and_solve(GpWorkspace* w, bool with_inverse, const char* who, hipStream_t s) {
+int factor_and_solve(GpWorkspace* w, int mode, const char* who, hipStream_t s, double* neg_rowsq) {
     const int64_t np = w->np;
     NNGP_TRY(potrf_f64(w->a, np, np, w->dinv, w->status, s));
     NNGP_TRY(potrf_f64_status(w->status, s, who));
     NNGP_HIP_CHECK(hipMemcpyAsync(w->wrow, w->y, sizeof(double) * np, hipMemcpyDeviceToDevice, s));
     NNGP_TRY(trsm_fwd_f64(w->wrow, np, NB, w->a, np, w->dinv, np, w->t, false, s));
-    if (!with_inverse) return 0;
+    if (mode == kGpSolveW) return 0;
     hipLaunchKernelGGL(k_eye, dim3((unsigned)((np + 255) / 256), (unsigned)np), dim3(256), 0, s, w->zt, np, np);
     NNGP_HIP_CHECK(hipGetLastError());
     NNGP_TRY(trsm_fwd_f64(w->zt, np, np, w->a, np, w->dinv, np, w->t, true, s));
-    NNGP_TRY(launch_gemm_nt_f64(w->ainv, np, nullptr, 0, w->zt, np, w->zt, np, np, np, np, 1.0, 0.0, s));
-    hipLaunchKernelGGL(k_rowdot, dim3((unsigned)np), dim3(256), 0, s, w->zt, np, np, w->wrow, w->alpha, 0.0, nullptr, 0.0);
+    if (mode == kGpSolveInverse) NNGP_TRY(launch_gemm_nt_f64(w->ainv, np, nullptr, 0, w->zt, np, w->zt, np, np, np, np, 1.0, 0.0, s));
+    hipLaunchKernelGGL(k_rowdot, dim3((unsigned)np), dim3(256), 0, s, w->zt, np, np, w->wrow, w->alpha, 0.0, neg_rowsq, 0.0);
     NNGP_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -1,0 +1,262 @@
+// Shared between the NNGP marginal likelihood (nngp_mll.hip) and the leave-one-out objectives (nngp_loo.hip): the handle both
+// work on, the construction of A = K + r I, and the device code of the fused adjoint pass -- one pass over the lower 64 x 64
+// tiles that contracts dK/dtheta with two seed matrices entry by entry, without ever forming dK/dtheta.
+//
+//   seeds of the marginal likelihood:   alpha_i alpha_j                             and  A^-1_ij
+//   seeds of the leave-one-out loss:    1/2 (alpha_i u_j + u_i alpha_j)             and  C_ij = (A^-1 diag(bbar) A^-1)_ij
+// Everything else -- tiling, Gram staging, forward recursion, reverse sweep, the q = 0 and exact-diagonal rules, the fixed-order
+// reduction -- is one piece of code (adjoint_tile), so both objectives differentiate the same kernel.
+#pragma once
+#include "gp_f64.h"
+#include "f64_math.h"
+#include "trig_tab.h"
+
+#include <cmath>
+
+namespace nngp {
+
+constexpr int MT = kGpTile;    // tile edge of the fused gradient pass
+constexpr int MKC = 32;        // feature chunk staged in LDS
+constexpr int MLD = MKC + 1;   // LDS row stride (odd: the 16 rows a wave reads sit in different banks)
+constexpr double kPi = 3.14159265358979323846;
+constexpr int kMaxComp = 2 * NNGP_MAX_DENSE;  // gradient components of K
+constexpr int kRed = 8;                       // scalar sums of k_mll_diag and the finish kernels (see nngp_mll::red)
+constexpr int kRedLen = kRed + 4 + NNGP_MAX_DENSE + 2 * kMaxComp;
+constexpr int kLooVec = 6;                    // vectors of nngp_mll::loo
+
+struct MllArgs {
+    const double* x;      // [n, d]
+    const double* q;      // [n]: |x_i|^2 / d
+    int64_t n;
+    int d;
+    const double* ainv;   // [Np, ld]: the matrix seed (A^-1, or C for the leave-one-out loss), lower triangle read
+    int64_t ld;
+    const double* alpha;  // [Np]
+    const double* u;      // [Np]: A^-1 abar (leave-one-out loss only)
+    double* part;         // [2 ncomp][nparts]: the rank-one / rank-two half of every component, then the matrix half
+    int64_t nparts;
+};
+
+// NLC: room for n_dense <= NLC layers (the per-entry state lives in registers, so its size must be known at compile time).
+// LOO: the rank-two seed 1/2 (alpha_i u_j + u_i alpha_j) instead of alpha_i alpha_j.
+template <int NLC, bool LOO>
+__device__ __forceinline__ void adjoint_tile(const MllArgs& a, const ArchDev& arch) {
+    __shared__ __attribute__((aligned(16))) double sm[2 * MT * MLD];  // the two row panels, then the Gram tile [MT][MT + 1]
+    __shared__ double qs[NLC][2 * MT];  // rows | columns: q at the input of Dense layer l
+    __shared__ double rq[NLC][2 * MT];  // 1 / (4 pi q') with q' after Dense layer l; 0 where q' = 0 (the q = 0 rule)
+    __shared__ __attribute__((aligned(16))) double tab[65 * 4];
+    __shared__ double red[256];
+    static_assert(MT * (MT + 1) <= 2 * MT * MLD, "the Gram tile aliases the panels");
+    const int tid = threadIdx.x, tc = tid & 15, tr = tid >> 4;
+    const int nd = arch.n_dense;
+    const int64_t tn = (a.n + MT - 1) / MT;
+    int64_t ti, tj;
+    lower_tile(xcd_tile(blockIdx.x, tn * (tn + 1) / 2), &ti, &tj);
+    const int64_t i0 = ti * MT, j0 = tj * MT;
+    for (int e = tid; e < 65 * 4; e += 256) tab[e] = kTrigTab[e >> 2][e & 3];
+    if (tid < 2 * MT) {  // the q chain of the tile's rows and columns, in the kernel build's order of operations
+        const int64_t g = tid < MT ? i0 + tid : j0 + tid - MT;
+        double q = g < a.n ? a.q[g] : 0.0;
+#pragma unroll
+        for (int l = 0; l < NLC; ++l) {
+            if (l < nd) {
+                qs[l][tid] = q;
+                const double qp = fma(arch.w2[l], q, arch.b2[l]);
+                rq[l][tid] = qp > 0.0 ? 1.0 / (4.0 * kPi * qp) : 0.0;
+                if (l < nd - 1) q = arch.act[l] == NNGP_ACT_ABRELU ? arch.ap[l][2] * qp : 0.5 * qp;
+            }
+        }
+    }
+
+    // ---- Gram tile: rows i0 + tr + 16 p, columns j0 + tc + 16 q, features summed in order ----
+    double (*s1)[MLD] = reinterpret_cast<double (*)[MLD]>(sm);
+    double (*s2)[MLD] = reinterpret_cast<double (*)[MLD]>(sm + MT * MLD);
+    double acc[4][4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[p][q] = 0.0;
+    for (int k0 = 0; k0 < a.d; k0 += MKC) {
+        const int kc = a.d - k0 < MKC ? a.d - k0 : MKC;
+        for (int e = tid; e < MT * MKC; e += 256) {
+            const int r = e / MKC, k = e % MKC;
+            const int64_t i = i0 + r, j = j0 + r;
+            s1[r][k] = (k < kc && i < a.n) ? a.x[i * a.d + k0 + k] : 0.0;
+            s2[r][k] = (k < kc && j < a.n) ? a.x[j * a.d + k0 + k] : 0.0;
+        }
+        __syncthreads();
+        for (int k = 0; k < kc; ++k) {
+            double u[4], v[4];
+#pragma unroll
+            for (int p = 0; p < 4; ++p) u[p] = s1[tr + 16 * p][k];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[q] = s2[tc + 16 * q][k];
+#pragma unroll
+            for (int p = 0; p < 4; ++p)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) acc[p][q] = fma(u[p], v[q], acc[p][q]);
+        }
+        __syncthreads();
+    }
+    double (*gt)[MT + 1] = reinterpret_cast<double (*)[MT + 1]>(sm);
+    const double inv_d = 1.0 / (double)a.d;
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) gt[tr + 16 * p][tc + 16 * q] = acc[p][q] * inv_d;
+    __syncthreads();
+
+    // ---- per entry: forward recursion, then the adjoint sweep from both seeds ----
+    double ga[2 * NLC], gi[2 * NLC];
+#pragma unroll
+    for (int c = 0; c < 2 * NLC; ++c) ga[c] = gi[c] = 0.0;
+#pragma unroll 1
+    for (int e = 0; e < 16; ++e) {
+        const int ri = tr + 16 * (e >> 2), cj = tc + 16 * (e & 3);
+        const int64_t i = i0 + ri, j = j0 + cj;
+        if (i >= a.n || j > i) continue;  // padding, and the upper half of a diagonal tile (j <= i < n for every other entry)
+        const bool dg = i == j;
+        const double w = dg ? 1.0 : 2.0;  // the lower triangle stands for the whole square
+        double kb_a;
+        if constexpr (LOO) kb_a = w * (0.5 * (a.alpha[i] * a.u[j] + a.u[i] * a.alpha[j]));
+        else kb_a = w * (a.alpha[i] * a.alpha[j]);
+        double kb_i = w * a.ainv[i * a.ld + j];
+        double k = dg ? qs[0][ri] : gt[ri][cj];  // exact diagonal: q q' - k^2 == 0 holds exactly
+        double kin[NLC], ck[NLC], cs[NLC];  // per layer: k into Dense l; dK'/dk and (b - a)^2 s of the activation after it
+#pragma unroll
+        for (int l = 0; l < NLC; ++l) {
+            kin[l] = k;
+            ck[l] = 0.0;
+            cs[l] = 0.0;
+            if (l < nd - 1) {
+                const double v = arch.w2[l], c = arch.b2[l];
+                const bool ab = arch.act[l] == NNGP_ACT_ABRELU;
+                k = fma(v, k, c);
+                if (dg) {  // theta = 0: K' = (a^2 + b^2) / 2 k  (1/2 for ReLU), no q dependence
+                    const double kd = ab ? arch.ap[l][2] : 0.5;
+                    k *= kd;
+                    ck[l] = kd;
+                } else {
+                    const double q1 = fma(v, qs[l][ri], c), q2 = fma(v, qs[l][MT + cj], c);
+                    const double rr = fma(q1, q2, -k * k);
+                    const double s = rr > 0.0 ? fast_sqrt_pos(rr > 0.0 ? rr : 1.0) : 0.0;
+                    const double kr = pi_minus_atan2(s, k, tab) * (0.5 / kPi);  // kdot
+                    const double kk = fma(kr, k, s * (0.5 / kPi));
+                    if (ab) {
+                        k = fma(arch.ap[l][0], k, arch.ap[l][1] * kk);
+                        ck[l] = fma(arch.ap[l][1], kr, arch.ap[l][0]);
+                        cs[l] = arch.ap[l][1] * s;
+                    } else {
+                        k = kk;
+                        ck[l] = kr;
+                        cs[l] = s;
+                    }
+                }
+            }
+        }
+        double q1a = 0.0, q2a = 0.0, q1i = 0.0, q2i = 0.0;
+#pragma unroll
+        for (int l = NLC - 1; l >= 0; --l) {
+            if (l < nd) {
+                if (l < nd - 1) {  // the activation after Dense layer l: dK'/dq1 = (b - a)^2 s / (4 pi q1'), q' = h q
+                    const double h = arch.act[l] == NNGP_ACT_ABRELU ? arch.ap[l][2] : 0.5;
+                    const double t1 = cs[l] * rq[l][ri], t2 = cs[l] * rq[l][MT + cj];
+                    q1a = fma(kb_a, t1, h * q1a);
+                    q2a = fma(kb_a, t2, h * q2a);
+                    kb_a *= ck[l];
+                    q1i = fma(kb_i, t1, h * q1i);
+                    q2i = fma(kb_i, t2, h * q2i);
+                    kb_i *= ck[l];
+                }
+                // Dense layer l: k' = v k + c (likewise q1, q2)
+                const double v = arch.w2[l], x1 = qs[l][ri], x2 = qs[l][MT + cj];
+                ga[2 * l] += fma(kb_a, kin[l], fma(q1a, x1, q2a * x2));
+                ga[2 * l + 1] += kb_a + q1a + q2a;
+                gi[2 * l] += fma(kb_i, kin[l], fma(q1i, x1, q2i * x2));
+                gi[2 * l + 1] += kb_i + q1i + q2i;
+                kb_a *= v;
+                q1a *= v;
+                q2a *= v;
+                kb_i *= v;
+                q1i *= v;
+                q2i *= v;
+            }
+        }
+    }
+    const int ncomp = 2 * nd;
+#pragma unroll
+    for (int c = 0; c < 2 * NLC; ++c) {
+        if (c < ncomp) {  // uniform over the workgroup
+            const double ra = block_sum(ga[c], red);
+            const double rb = block_sum(gi[c], red);
+            if (tid == 0) {
+                a.part[(int64_t)c * a.nparts + blockIdx.x] = ra;
+                a.part[(int64_t)(ncomp + c) * a.nparts + blockIdx.x] = rb;
+            }
+        }
+    }
+}
+
+// out[e] = sum_i q_i^(e), the diagonal's q at the input of Dense layer e (one workgroup, fixed order): tr dK/dtheta follows from
+// these in closed form (trace_dk)
+__device__ __forceinline__ void finish_qsums(const double* q, int64_t n, const ArchDev& arch, double* red, double* out) {
+    const int nd = arch.n_dense;
+    double sq[NNGP_MAX_DENSE];
+#pragma unroll
+    for (int e = 0; e < NNGP_MAX_DENSE; ++e) sq[e] = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += 256) {
+        double z = q[i];
+#pragma unroll
+        for (int e = 0; e < NNGP_MAX_DENSE; ++e) {
+            if (e < nd) {
+                sq[e] += z;
+                const double zp = fma(arch.w2[e], z, arch.b2[e]);
+                if (e < nd - 1) z = arch.act[e] == NNGP_ACT_ABRELU ? arch.ap[e][2] * zp : 0.5 * zp;
+            }
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < NNGP_MAX_DENSE; ++e) {
+        if (e < nd) {
+            const double r = block_sum(sq[e], red);
+            if (threadIdx.x == 0) out[e] = r;
+        }
+    }
+}
+
+// tr dK / dtheta from the diagonal's closed form: K_ii = u_{nd-1}, u_l = v_l z_l + c_l, z_{l+1} = h_l u_l, so
+// dK_ii / du_l = prod_{m >= l, hidden} h_m prod_{m > l} v_m =: D_l and tr dK/dv_l = D_l sum_i z_l,i, tr dK/dc_l = D_l N
+inline void trace_dk(const ArchDev& arch, const double* sq, double dn, double* trdk) {
+    const int nd = arch.n_dense;
+    double dl = 1.0;
+    for (int l = nd - 1; l >= 0; --l) {
+        if (l < nd - 1) dl *= arch.act[l] == NNGP_ACT_ABRELU ? arch.ap[l][2] : 0.5;
+        trdk[2 * l] = dl * sq[l];
+        trdk[2 * l + 1] = dl * dn;
+        dl *= arch.w2[l];
+    }
+}
+
+}  // namespace nngp
+
+// The handle of include/nngp_mll.h and include/nngp_loo.h
+struct nngp_mll {
+    nngp::GpWorkspace w;      // part: 2 kMaxComp per tile; red: [0, 2) tr K, r; [kRed, ...) the finish kernels' sums
+    double* q = nullptr;      // n_cap: |x_i|^2 / d
+    double* loo = nullptr;    // kLooVec x np_cap: -b, abar, bbar, u, the leave-one-out means and variances
+    int n_dense = 0;
+    bool have_terms = false;
+    double terms[2 * (nngp::kMaxComp + 1) + 5 + nngp::kMaxComp] = {};
+    int n_terms = 0;
+    int loo_get = 0;          // NNGP_GET_* of the last leave-one-out evaluation (0: none, or the data changed since)
+    bool have_loo_terms = false;
+    double loo_terms[2 * (nngp::kMaxComp + 1) + 3 + nngp::kMaxComp] = {};
+    int n_loo_terms = 0;
+};
+
+namespace nngp {
+// nngp_mll.hip: the architecture checked for the float64 gradient paths (rc -2 naming `who`), and A = K + r I (get: NNGP_GET_NNGP,
+// or NNGP_GET_NTK for Theta + r I) in w.a with the identity on the padding; red[0] = tr K, red[1] = r
+int mll_make_arch(const nngp_arch_act* arch_in, double diag_reg, const char* who, ArchDev* arch);
+int mll_build_a(nngp_mll* h, const ArchDev& arch, int get, double diag_reg, int absolute, hipStream_t s);
+}  // namespace nngp

@@ -16,35 +16,13 @@
 //   k_mll_finish         one workgroup, fixed order: the partial vectors, sum log L_ii, |w|^2, alpha^T alpha, tr A^-1 and the
 //                        per-layer sums of the diagonal's q chain (tr dK/dtheta follows from them in closed form)
 // No atomics anywhere: repeated evaluations are bit-identical.
-#include "gp_f64.h"
-#include "f64_math.h"
-#include "trig_tab.h"
+#include "nngp_adjoint.h"
 
-#include <cmath>
 #include <vector>
 
 namespace nngp {
 
 namespace {
-
-constexpr int MT = kGpTile;    // tile edge of the fused gradient pass
-constexpr int MKC = 32;        // feature chunk staged in LDS
-constexpr int MLD = MKC + 1;   // LDS row stride (odd: the 16 rows a wave reads sit in different banks)
-constexpr double kPi = 3.14159265358979323846;
-constexpr int kMaxComp = 2 * NNGP_MAX_DENSE;  // gradient components of K
-constexpr int kRed = 8;                       // scalar sums of k_mll_diag / k_mll_finish (see nngp_mll::red)
-
-struct MllArgs {
-    const double* x;      // [n, d]
-    const double* q;      // [n]: |x_i|^2 / d
-    int64_t n;
-    int d;
-    const double* ainv;   // [Np, ld]: A^-1
-    int64_t ld;
-    const double* alpha;  // [Np]
-    double* part;         // [2 ncomp][nparts]: the alpha alpha^T half of every component, then the A^-1 half
-    int64_t nparts;
-};
 
 __global__ __launch_bounds__(256) void k_mll_pad(double* a, int64_t ld, int64_t n, int64_t np) {
     const int64_t i = blockIdx.x;
@@ -65,161 +43,10 @@ __global__ __launch_bounds__(256) void k_mll_diag(double* a, int64_t ld, int64_t
     }
 }
 
-// NLC: room for n_dense <= NLC layers (the per-entry state lives in registers, so its size must be known at compile time).
+// the fused adjoint pass (nngp_adjoint.h) from the seeds alpha_i alpha_j and A^-1_ij
 template <int NLC>
 __global__ __launch_bounds__(256) void k_nngp_mll_partial(MllArgs a, ArchDev arch) {
-    __shared__ __attribute__((aligned(16))) double sm[2 * MT * MLD];  // the two row panels, then the Gram tile [MT][MT + 1]
-    __shared__ double qs[NLC][2 * MT];  // rows | columns: q at the input of Dense layer l
-    __shared__ double rq[NLC][2 * MT];  // 1 / (4 pi q') with q' after Dense layer l; 0 where q' = 0 (the q = 0 rule)
-    __shared__ __attribute__((aligned(16))) double tab[65 * 4];
-    __shared__ double red[256];
-    static_assert(MT * (MT + 1) <= 2 * MT * MLD, "the Gram tile aliases the panels");
-    const int tid = threadIdx.x, tc = tid & 15, tr = tid >> 4;
-    const int nd = arch.n_dense;
-    const int64_t tn = (a.n + MT - 1) / MT;
-    int64_t ti, tj;
-    lower_tile(xcd_tile(blockIdx.x, tn * (tn + 1) / 2), &ti, &tj);
-    const int64_t i0 = ti * MT, j0 = tj * MT;
-    for (int e = tid; e < 65 * 4; e += 256) tab[e] = kTrigTab[e >> 2][e & 3];
-    if (tid < 2 * MT) {  // the q chain of the tile's rows and columns, in the kernel build's order of operations
-        const int64_t g = tid < MT ? i0 + tid : j0 + tid - MT;
-        double q = g < a.n ? a.q[g] : 0.0;
-#pragma unroll
-        for (int l = 0; l < NLC; ++l) {
-            if (l < nd) {
-                qs[l][tid] = q;
-                const double qp = fma(arch.w2[l], q, arch.b2[l]);
-                rq[l][tid] = qp > 0.0 ? 1.0 / (4.0 * kPi * qp) : 0.0;
-                if (l < nd - 1) q = arch.act[l] == NNGP_ACT_ABRELU ? arch.ap[l][2] * qp : 0.5 * qp;
-            }
-        }
-    }
-
-    // ---- Gram tile: rows i0 + tr + 16 p, columns j0 + tc + 16 q, features summed in order ----
-    double (*s1)[MLD] = reinterpret_cast<double (*)[MLD]>(sm);
-    double (*s2)[MLD] = reinterpret_cast<double (*)[MLD]>(sm + MT * MLD);
-    double acc[4][4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc[p][q] = 0.0;
-    for (int k0 = 0; k0 < a.d; k0 += MKC) {
-        const int kc = a.d - k0 < MKC ? a.d - k0 : MKC;
-        for (int e = tid; e < MT * MKC; e += 256) {
-            const int r = e / MKC, k = e % MKC;
-            const int64_t i = i0 + r, j = j0 + r;
-            s1[r][k] = (k < kc && i < a.n) ? a.x[i * a.d + k0 + k] : 0.0;
-            s2[r][k] = (k < kc && j < a.n) ? a.x[j * a.d + k0 + k] : 0.0;
-        }
-        __syncthreads();
-        for (int k = 0; k < kc; ++k) {
-            double u[4], v[4];
-#pragma unroll
-            for (int p = 0; p < 4; ++p) u[p] = s1[tr + 16 * p][k];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) v[q] = s2[tc + 16 * q][k];
-#pragma unroll
-            for (int p = 0; p < 4; ++p)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[p][q] = fma(u[p], v[q], acc[p][q]);
-        }
-        __syncthreads();
-    }
-    double (*gt)[MT + 1] = reinterpret_cast<double (*)[MT + 1]>(sm);
-    const double inv_d = 1.0 / (double)a.d;
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) gt[tr + 16 * p][tc + 16 * q] = acc[p][q] * inv_d;
-    __syncthreads();
-
-    // ---- per entry: forward recursion, then the adjoint sweep from both seeds ----
-    double ga[2 * NLC], gi[2 * NLC];
-#pragma unroll
-    for (int c = 0; c < 2 * NLC; ++c) ga[c] = gi[c] = 0.0;
-#pragma unroll 1
-    for (int e = 0; e < 16; ++e) {
-        const int ri = tr + 16 * (e >> 2), cj = tc + 16 * (e & 3);
-        const int64_t i = i0 + ri, j = j0 + cj;
-        if (i >= a.n || j > i) continue;  // padding, and the upper half of a diagonal tile (j <= i < n for every other entry)
-        const bool dg = i == j;
-        const double w = dg ? 1.0 : 2.0;  // the lower triangle stands for the whole square
-        double kb_a = w * (a.alpha[i] * a.alpha[j]);
-        double kb_i = w * a.ainv[i * a.ld + j];
-        double k = dg ? qs[0][ri] : gt[ri][cj];  // exact diagonal: q q' - k^2 == 0 holds exactly
-        double kin[NLC], ck[NLC], cs[NLC];  // per layer: k into Dense l; dK'/dk and (b - a)^2 s of the activation after it
-#pragma unroll
-        for (int l = 0; l < NLC; ++l) {
-            kin[l] = k;
-            ck[l] = 0.0;
-            cs[l] = 0.0;
-            if (l < nd - 1) {
-                const double v = arch.w2[l], c = arch.b2[l];
-                const bool ab = arch.act[l] == NNGP_ACT_ABRELU;
-                k = fma(v, k, c);
-                if (dg) {  // theta = 0: K' = (a^2 + b^2) / 2 k  (1/2 for ReLU), no q dependence
-                    const double kd = ab ? arch.ap[l][2] : 0.5;
-                    k *= kd;
-                    ck[l] = kd;
-                } else {
-                    const double q1 = fma(v, qs[l][ri], c), q2 = fma(v, qs[l][MT + cj], c);
-                    const double rr = fma(q1, q2, -k * k);
-                    const double s = rr > 0.0 ? fast_sqrt_pos(rr > 0.0 ? rr : 1.0) : 0.0;
-                    const double kr = pi_minus_atan2(s, k, tab) * (0.5 / kPi);  // kdot
-                    const double kk = fma(kr, k, s * (0.5 / kPi));
-                    if (ab) {
-                        k = fma(arch.ap[l][0], k, arch.ap[l][1] * kk);
-                        ck[l] = fma(arch.ap[l][1], kr, arch.ap[l][0]);
-                        cs[l] = arch.ap[l][1] * s;
-                    } else {
-                        k = kk;
-                        ck[l] = kr;
-                        cs[l] = s;
-                    }
-                }
-            }
-        }
-        double q1a = 0.0, q2a = 0.0, q1i = 0.0, q2i = 0.0;
-#pragma unroll
-        for (int l = NLC - 1; l >= 0; --l) {
-            if (l < nd) {
-                if (l < nd - 1) {  // the activation after Dense layer l: dK'/dq1 = (b - a)^2 s / (4 pi q1'), q' = h q
-                    const double h = arch.act[l] == NNGP_ACT_ABRELU ? arch.ap[l][2] : 0.5;
-                    const double t1 = cs[l] * rq[l][ri], t2 = cs[l] * rq[l][MT + cj];
-                    q1a = fma(kb_a, t1, h * q1a);
-                    q2a = fma(kb_a, t2, h * q2a);
-                    kb_a *= ck[l];
-                    q1i = fma(kb_i, t1, h * q1i);
-                    q2i = fma(kb_i, t2, h * q2i);
-                    kb_i *= ck[l];
-                }
-                // Dense layer l: k' = v k + c (likewise q1, q2)
-                const double v = arch.w2[l], x1 = qs[l][ri], x2 = qs[l][MT + cj];
-                ga[2 * l] += fma(kb_a, kin[l], fma(q1a, x1, q2a * x2));
-                ga[2 * l + 1] += kb_a + q1a + q2a;
-                gi[2 * l] += fma(kb_i, kin[l], fma(q1i, x1, q2i * x2));
-                gi[2 * l + 1] += kb_i + q1i + q2i;
-                kb_a *= v;
-                q1a *= v;
-                q2a *= v;
-                kb_i *= v;
-                q1i *= v;
-                q2i *= v;
-            }
-        }
-    }
-    const int ncomp = 2 * nd;
-#pragma unroll
-    for (int c = 0; c < 2 * NLC; ++c) {
-        if (c < ncomp) {  // uniform over the workgroup
-            const double ra = block_sum(ga[c], red);
-            const double rb = block_sum(gi[c], red);
-            if (tid == 0) {
-                a.part[(int64_t)c * a.nparts + blockIdx.x] = ra;
-                a.part[(int64_t)(ncomp + c) * a.nparts + blockIdx.x] = rb;
-            }
-        }
-    }
+    adjoint_tile<NLC, false>(a, arch);
 }
 
 // One workgroup, fixed order.  out[0] = sum log L_ii, out[1] = |w|^2 (= y^T A^-1 y), out[2] = alpha^T alpha, out[3] = tr A^-1,
@@ -235,27 +62,7 @@ __global__ __launch_bounds__(256) void k_mll_finish(const double* l, int64_t ldl
         for (int c = 0; c < 4; ++c) out[c] = s[c];
     if (!alpha) return;
     const int nd = arch.n_dense;
-    double sq[NNGP_MAX_DENSE];
-#pragma unroll
-    for (int e = 0; e < NNGP_MAX_DENSE; ++e) sq[e] = 0.0;
-    for (int64_t i = threadIdx.x; i < n; i += 256) {
-        double z = q[i];
-#pragma unroll
-        for (int e = 0; e < NNGP_MAX_DENSE; ++e) {
-            if (e < nd) {
-                sq[e] += z;
-                const double zp = fma(arch.w2[e], z, arch.b2[e]);
-                if (e < nd - 1) z = arch.act[e] == NNGP_ACT_ABRELU ? arch.ap[e][2] * zp : 0.5 * zp;
-            }
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < NNGP_MAX_DENSE; ++e) {
-        if (e < nd) {
-            const double r = block_sum(sq[e], red);
-            if (threadIdx.x == 0) out[4 + e] = r;
-        }
-    }
+    finish_qsums(q, n, arch, red, out + 4);
     for (int c = 0; c < 4 * nd; ++c) {
         const double r = finish_part(part, nparts, c, red);
         if (threadIdx.x == 0) out[4 + nd + c] = r;
@@ -275,6 +82,44 @@ int launch_mll_partial(const MllArgs& a, const ArchDev& arch, hipStream_t s) {
 
 }  // namespace
 
+int mll_make_arch(const nngp_arch_act* arch_in, double diag_reg, const char* who, ArchDev* out) {
+    ArchDev& arch = *out;
+    NNGP_TRY(make_arch_dev_act(arch_in, &arch));
+    const int nd = arch.n_dense;
+    for (int l = 0; l < nd; ++l) {
+        const double w = arch_in->base.w_std[l], b = arch_in->base.b_std[l];
+        NNGP_REQUIRE(std::isfinite(w) && std::isfinite(b) && w >= 0.0 && b >= 0.0,
+                     "%s: w_std / b_std of Dense layer %d must be finite and non-negative (%g, %g)", who, l, w, b);
+    }
+    for (int l = 0; l < nd - 1; ++l)
+        NNGP_REQUIRE(arch.act[l] != NNGP_ACT_ERF, "%s: hidden layer %d is Erf; the gradient covers ReLU and ABRelu only", who, l);
+    NNGP_REQUIRE(std::isfinite(diag_reg) && diag_reg >= 0.0, "%s: diag_reg must be finite and non-negative (%g)", who, diag_reg);
+    return 0;
+}
+
+// K (or Theta) by the kernel build (per-layer recursion: no_comp), the padding the identity, r on the diagonal
+int mll_build_a(nngp_mll* h, const ArchDev& arch, int get, double diag_reg, int absolute, hipStream_t s) {
+    GpWorkspace& w = h->w;
+    const int64_t n = w.n, np = w.np;
+    BuildArgs b{};
+    b.x1 = b.x2 = w.x;
+    b.q1 = b.q2 = h->q;
+    b.n1 = b.n2 = n;
+    b.d = w.d;
+    b.row_begin = 0;
+    b.row_end = n;
+    b.sym = 1;
+    if (get == NNGP_GET_NTK) b.ntk64 = w.a;
+    else b.nngp64 = w.a;
+    b.ld64 = np;
+    b.no_comp = 1;
+    NNGP_TRY(launch_kernel_build(b, arch, s));
+    hipLaunchKernelGGL(k_mll_pad, dim3((unsigned)np), dim3(256), 0, s, w.a, np, n, np);
+    hipLaunchKernelGGL(k_mll_diag, dim3(1), dim3(256), 0, s, w.a, np, n, diag_reg, (int)(absolute != 0), w.red);
+    NNGP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 }  // namespace nngp
 
 using namespace nngp;
@@ -282,17 +127,9 @@ using namespace nngp;
 // ---------------------------------------------------------------------------------------------------------------------------
 // C ABI (include/nngp_mll.h)
 
-struct nngp_mll {
-    GpWorkspace w;            // part: 2 kMaxComp per tile; red: [0, 2) tr K, r; [kRed, ...) k_mll_finish's sums
-    double* q = nullptr;      // n_cap: |x_i|^2 / d
-    int n_dense = 0;
-    bool have_terms = false;
-    double terms[2 * (kMaxComp + 1) + 5 + kMaxComp] = {};
-    int n_terms = 0;
-};
-
 static void mll_free(nngp_mll* h) {
     dev_free(h->q);
+    dev_free(h->loo);
     ws_free(&h->w);
 }
 
@@ -303,8 +140,12 @@ int nngp_mll_create(nngp_mll** out, int64_t n_cap, int32_t d) {
     *out = nullptr;
     nngp_mll* h = new (std::nothrow) nngp_mll();
     NNGP_REQUIRE(h != nullptr, "mll_create: out of host memory");
+    // solve scratch: Np x 128 for the triangular solves; (Np / 128) x Np for the symmetric product u = A^-1 abar of the
+    // leave-one-out gradient (launch_symv_f64's partial rows), whichever is larger
+    const int64_t np_cap = round_up(n_cap, TB), blocks = np_cap / TB;
     int rc = dev_alloc(&h->q, n_cap);
-    if (rc == 0) rc = ws_alloc(&h->w, n_cap, d, 2 * kMaxComp, kRed + 4 + NNGP_MAX_DENSE + 2 * kMaxComp, round_up(n_cap, TB));
+    if (rc == 0) rc = dev_alloc(&h->loo, kLooVec * np_cap);
+    if (rc == 0) rc = ws_alloc(&h->w, n_cap, d, 2 * kMaxComp, kRedLen, blocks * blocks > np_cap ? blocks * blocks : np_cap);
     if (rc != 0) {
         mll_free(h);
         delete h;
@@ -327,7 +168,8 @@ int nngp_mll_set_train(nngp_mll* h, const double* x, const double* y, int64_t n,
     NNGP_REQUIRE(h != nullptr && x != nullptr && y != nullptr, "mll_set_train: NULL argument");
     NNGP_REQUIRE(ny == 1, "mll_set_train: the marginal likelihood takes one output column (ny=%d)", ny);
     NNGP_REQUIRE(n >= 1 && n <= h->w.n_cap, "mll_set_train: n=%lld outside [1, n_cap=%lld]", (long long)n, (long long)h->w.n_cap);
-    h->have_terms = false;
+    h->have_terms = h->have_loo_terms = false;
+    h->loo_get = 0;
     NNGP_TRY(launch_row_sqnorm(x, n, h->w.d, h->q, s));  // from the caller's x: ws_set_train's synchronise covers it
     return ws_set_train(&h->w, x, y, hipMemcpyDeviceToDevice, n, s);
 }
@@ -338,47 +180,23 @@ int nngp_mll_evaluate(nngp_mll* h, const nngp_arch_act* arch_in, double diag_reg
     NNGP_REQUIRE(h != nullptr && arch_in != nullptr && nlml != nullptr, "mll_evaluate: NULL argument");
     NNGP_REQUIRE(h->w.n > 0, "mll_evaluate: no training data (nngp_mll_set_train)");
     ArchDev arch{};
-    NNGP_TRY(make_arch_dev_act(arch_in, &arch));
+    NNGP_TRY(mll_make_arch(arch_in, diag_reg, "mll_evaluate", &arch));
     const int nd = arch.n_dense;
-    for (int l = 0; l < nd; ++l) {
-        const double w = arch_in->base.w_std[l], b = arch_in->base.b_std[l];
-        NNGP_REQUIRE(std::isfinite(w) && std::isfinite(b) && w >= 0.0 && b >= 0.0,
-                     "mll_evaluate: w_std / b_std of Dense layer %d must be finite and non-negative (%g, %g)", l, w, b);
-    }
-    for (int l = 0; l < nd - 1; ++l)
-        NNGP_REQUIRE(arch.act[l] != NNGP_ACT_ERF, "mll_evaluate: hidden layer %d is Erf; the gradient covers ReLU and ABRelu only", l);
-    NNGP_REQUIRE(std::isfinite(diag_reg) && diag_reg >= 0.0, "mll_evaluate: diag_reg must be finite and non-negative (%g)", diag_reg);
     GpWorkspace& w = h->w;
     w.factored = h->have_terms = false;
     const int64_t n = w.n, np = w.np;
-
-    // A = K + r I: K by the kernel build (per-layer recursion: no_comp), the padding the identity
-    BuildArgs b{};
-    b.x1 = b.x2 = w.x;
-    b.q1 = b.q2 = h->q;
-    b.n1 = b.n2 = n;
-    b.d = w.d;
-    b.row_begin = 0;
-    b.row_end = n;
-    b.sym = 1;
-    b.nngp64 = w.a;
-    b.ld64 = np;
-    b.no_comp = 1;
-    NNGP_TRY(launch_kernel_build(b, arch, s));
-    hipLaunchKernelGGL(k_mll_pad, dim3((unsigned)np), dim3(256), 0, s, w.a, np, n, np);
-    hipLaunchKernelGGL(k_mll_diag, dim3(1), dim3(256), 0, s, w.a, np, n, diag_reg, (int)(absolute != 0), w.red);
-    NNGP_HIP_CHECK(hipGetLastError());
+    NNGP_TRY(mll_build_a(h, arch, NNGP_GET_NNGP, diag_reg, absolute, s));
     const bool want = grad != nullptr;
     NNGP_TRY(factor_and_solve(&w, want, "mll_evaluate", s));
     const int64_t nparts = gp_lower_tiles(n);
     if (want) {
-        MllArgs ma{w.x, h->q, n, w.d, w.ainv, np, w.alpha, w.part, nparts};
+        MllArgs ma{w.x, h->q, n, w.d, w.ainv, np, w.alpha, nullptr, w.part, nparts};
         NNGP_TRY(launch_mll_partial(ma, arch, s));
     }
     hipLaunchKernelGGL(k_mll_finish, dim3(1), dim3(256), 0, s, w.a, np, n, w.wrow, want ? w.part : nullptr, nparts,
                        want ? w.alpha : nullptr, w.ainv, h->q, arch, w.red + kRed);
     NNGP_HIP_CHECK(hipGetLastError());
-    double r[kRed + 4 + NNGP_MAX_DENSE + 2 * kMaxComp];
+    double r[kRedLen];
     NNGP_HIP_CHECK(hipMemcpyAsync(r, w.red, sizeof(r), hipMemcpyDeviceToHost, s));
     NNGP_HIP_CHECK(hipStreamSynchronize(s));
     const double tr_k = r[0], logdet_half = r[kRed], yay = r[kRed + 1];
@@ -392,16 +210,8 @@ int nngp_mll_evaluate(nngp_mll* h, const nngp_arch_act* arch_in, double diag_reg
     const double* pa = sq + nd;         // alpha alpha^T halves of the K components
     const double* pi = pa + 2 * nd;     // A^-1 halves
     const int ncomp = 2 * nd;
-    // tr dK / dtheta from the diagonal's closed form: K_ii = u_{nd-1}, u_l = v_l z_l + c_l, z_{l+1} = h_l u_l, so
-    // dK_ii / du_l = prod_{m >= l, hidden} h_m prod_{m > l} v_m =: D_l and tr dK/dv_l = D_l sum_i z_l,i, tr dK/dc_l = D_l N
     double trdk[kMaxComp];
-    double dl = 1.0;
-    for (int l = nd - 1; l >= 0; --l) {
-        if (l < nd - 1) dl *= arch.act[l] == NNGP_ACT_ABRELU ? arch.ap[l][2] : 0.5;
-        trdk[2 * l] = dl * sq[l];
-        trdk[2 * l + 1] = dl * dn;
-        dl *= arch.w2[l];
-    }
+    trace_dk(arch, sq, dn, trdk);
     double* t = h->terms;
     for (int p = 0; p <= ncomp; ++p) {
         double qa, ta;  // alpha^T dA_p alpha, tr(A^-1 dA_p)

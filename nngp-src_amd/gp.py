@@ -28,13 +28,14 @@ def softplus(x):
     return np.logaddexp(x, 0.)
 
 
-def train_hyperparameters(evaluate, raw0=RAW0, steps=STEPS, lr=LR, report=print):
+def train_hyperparameters(evaluate, raw0=RAW0, steps=STEPS, lr=LR, report=print, label="neg marginal likelihood"):
     """The reference's ``train_step`` loop (train.py:136-148) over ``evaluate(raw, with_grad) -> (nlml, grad or None)``.
 
     Per raw parameter (any number of them; mll.tune_hyperparameters drives it too): ``m = 0.9 m + 0.1 g``, ``s = 0.9 s + 0.1 g^2``, ``p -= lr m / sqrt(s + 1e-5)``, from ``m = 0``
     and ``s = 1`` (the reference's ``scales = p * 0. + 1.``).  After each step the NLML at the new point is reported as
     ``"Step: %d, neg marginal likelihood: %f"``; that point's gradient comes from the same evaluation, so ``steps`` steps
-    cost ``steps + 1`` evaluations.  Returns the final raw parameters and the list of reported NLMLs."""
+    cost ``steps + 1`` evaluations.  ``label`` names the objective in that line (loo.tune_hyperparameters: ``"LOO nlpd"``).
+    Returns the final raw parameters and the list of reported NLMLs."""
     raw = np.array(raw0, dtype=np.float64)
     m = np.zeros_like(raw)
     s = np.ones_like(raw)
@@ -48,7 +49,7 @@ def train_hyperparameters(evaluate, raw0=RAW0, steps=STEPS, lr=LR, report=print)
         nlml, g = evaluate(raw, i + 1 < steps)
         history.append(nlml)
         if report is not None:
-            report("Step: %d, neg marginal likelihood: %f" % (i, nlml))
+            report("Step: %%d, %s: %%f" % label % (i, nlml))
     return raw, history
 
 

@@ -78,8 +78,23 @@ def NNGP_train_and_test(args, X_train, Y_train, X_test, Y_test, query_infos_trai
 
     errors = np.ravel(np.array(pred_mean - Y_test))
     pred_stat.get_prediction_details(errors, query_infos_test, partition_keys='num_table')
-    return {"pred_mean": np.ravel(pred_mean), "pred_std": np.ravel(pred_std), "errors": errors, "mse": float(mse),
-            "fit_info": predict_fn.model_for(args.kernel_type).info()}
+    res = {"pred_mean": np.ravel(pred_mean), "pred_std": np.ravel(pred_std), "errors": errors, "mse": float(mse),
+           "fit_info": predict_fn.model_for(args.kernel_type).info()}
+    if getattr(args, "loo", False):
+        res.update(loo_profile(args, kernel_fn, X_train, Y_train, query_infos_train, diag_reg))
+    return res
+
+
+def loo_profile(args, kernel_fn, X_train, Y_train, query_infos_train=None, diag_reg=1e-3):
+    """--loo: the leave-one-out residuals of the fit over the training split (loo.py) -- every training query predicted as if
+    it had been held out -- as "LOO Mean Square Error: ..." (the mean of their squares) and their q-error profile."""
+    from . import loo
+    loo_mean, loo_var = loo.loo_predict(kernel_fn, X_train, Y_train, diag_reg=diag_reg, get=args.kernel_type)
+    loo_errors = loo_mean - np.ravel(np.asarray(Y_train, dtype=np.float64))
+    loo_mse = float(np.mean(np.power(loo_errors, 2)))
+    print("LOO Mean Square Error: {}".format(loo_mse))
+    pred_stat.get_prediction_details(loo_errors, query_infos_train, partition_keys='num_table')
+    return {"loo_mean": loo_mean, "loo_var": loo_var, "loo_errors": loo_errors, "loo_mse": loo_mse}
 
 
 def load_training_data(args):
@@ -102,12 +117,22 @@ def load_training_data(args):
     return X, Y, all_query_infos
 
 
+TUNE_OBJECTIVES = ("mll", "loo_nlpd", "loo_mse")
+
+
 def tune_kernel_fn(args, X_train, Y_train):
-    """--tune_hyper STEPS: W_std / b_std / diag_reg of the NNGP by marginal likelihood on the training split (mll.py)."""
-    from . import mll
+    """--tune_hyper STEPS: W_std / b_std / diag_reg of the NNGP on the training split, by marginal likelihood (mll.py) or, with
+    --tune_objective loo_nlpd / loo_mse, by a leave-one-out objective (loo.py)."""
+    from . import loo, mll
     _, _, kernel_fn = kernel_fn_from_args(args)
-    kernel_fn, diag_reg, _ = mll.tune_hyperparameters(kernel_fn, X_train, Y_train, diag_reg=1e-3, steps=args.tune_hyper,
-                                                      lr=args.tune_lr, b_std_init=args.b_std_init)
+    objective = getattr(args, "tune_objective", "mll")
+    if objective == "mll":
+        kernel_fn, diag_reg, _ = mll.tune_hyperparameters(kernel_fn, X_train, Y_train, diag_reg=1e-3, steps=args.tune_hyper,
+                                                          lr=args.tune_lr, b_std_init=args.b_std_init)
+    else:
+        kernel_fn, diag_reg, _ = loo.tune_hyperparameters(kernel_fn, X_train, Y_train, diag_reg=1e-3, steps=args.tune_hyper,
+                                                          lr=args.tune_lr, b_std_init=args.b_std_init,
+                                                          objective=objective[len("loo_"):])
     print("Tuned W_std={} b_std={} diag_reg={}".format(list(kernel_fn.w_std), list(kernel_fn.b_std), diag_reg))
     return kernel_fn, diag_reg
 
@@ -115,7 +140,7 @@ def tune_kernel_fn(args, X_train, Y_train):
 def main(args):
     tune = getattr(args, "tune_hyper", 0) or 0
     if tune and args.kernel_type != 'nngp':
-        raise ValueError("--tune_hyper tunes the NNGP posterior's marginal likelihood: it needs --kernel_type nngp")
+        raise ValueError("--tune_hyper tunes the NNGP posterior (marginal likelihood or leave-one-out): it needs --kernel_type nngp")
     if args.join_query:
         raise NotImplementedError("join schemas need their benchmark CSVs; use Estimator(encoder=...)")
     X, Y, all_query_infos = load_training_data(args)
@@ -157,6 +182,10 @@ def make_parser():
     parser.add_argument("--full_cov", action='store_true', help="form the full M x M covariance like the reference")
     parser.add_argument("--tune_hyper", type=int, default=0,
                         help="steps of marginal-likelihood tuning of W_std / b_std / diag_reg before the fit (nngp only; 0: off)")
+    parser.add_argument("--tune_objective", type=str, default="mll", choices=TUNE_OBJECTIVES,
+                        help="what --tune_hyper minimises: the negative log marginal likelihood, or the leave-one-out nlpd / mse")
+    parser.add_argument("--loo", action='store_true',
+                        help="after the fit, also print the leave-one-out error and q-error profile over the training split (nngp, ntk)")
     parser.add_argument("--tune_lr", type=float, default=0.05, help="step size of --tune_hyper")
     parser.add_argument("--b_std_init", type=float, default=None, help="start of b_std for layers with b_std = 0 (--tune_hyper)")
     return parser
