@@ -54,6 +54,9 @@ MLL_ABI_SYMBOLS = ("nngp_mll_create", "nngp_mll_destroy", "nngp_mll_set_train", 
 LOO_ABI_SYMBOLS = ("nngp_mll_loo_evaluate", "nngp_mll_loo_predictions", "nngp_mll_loo_terms")
 LOO_NLPD, LOO_MSE = 0, 1
 
+# include/nngp_ard.h: per-feature input relevances on the nngp_mll handle; GPU library only (no host build)
+ARD_ABI_SYMBOLS = ("nngp_mll_reserve_ard", "nngp_mll_evaluate_ard", "nngp_mll_loo_evaluate_ard", "nngp_mll_ard_terms")
+
 
 class NngpArch(ctypes.Structure):
     _fields_ = [("n_dense", ctypes.c_int32), ("reserved", ctypes.c_int32),
@@ -102,6 +105,7 @@ def load(knobs: bool = False):
     bind_act_prototypes(lib)
     bind_mll_prototypes(lib)
     bind_loo_prototypes(lib)
+    bind_ard_prototypes(lib)
     _libs[knobs] = lib
     return lib
 
@@ -238,6 +242,19 @@ def bind_loo_prototypes(lib):
     lib.nngp_mll_loo_predictions.argtypes = [vp, vp, vp, vp]
     lib.nngp_mll_loo_terms.argtypes = [vp, ctypes.POINTER(dbl), i32]
     for name in LOO_ABI_SYMBOLS:
+        getattr(lib, name).restype = ctypes.c_int
+    return lib
+
+
+def bind_ard_prototypes(lib):
+    """Argument and result types of include/nngp_ard.h (the HIP library only)."""
+    vp, i32, dbl = ctypes.c_void_p, ctypes.c_int32, ctypes.c_double
+    pd = ctypes.POINTER(dbl)
+    lib.nngp_mll_reserve_ard.argtypes = [vp]
+    lib.nngp_mll_evaluate_ard.argtypes = [vp, ctypes.POINTER(NngpArchAct), pd, dbl, i32, pd, pd, pd, vp]
+    lib.nngp_mll_loo_evaluate_ard.argtypes = [vp, ctypes.POINTER(NngpArchAct), i32, pd, dbl, i32, i32, pd, pd, pd, vp]
+    lib.nngp_mll_ard_terms.argtypes = [vp, pd, i32]
+    for name in ARD_ABI_SYMBOLS:
         getattr(lib, name).restype = ctypes.c_int
     return lib
 

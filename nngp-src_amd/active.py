@@ -22,6 +22,10 @@ from .model import GPModel
 from .util import PredictionStatistics
 
 
+def _same_scale(a, b):
+    return (a is None and b is None) or (a is not None and b is not None and np.array_equal(a, b))
+
+
 class ActiveLearner(object):
     def __init__(self, args=None, budget=1000, active_iters=3, kernel_type="nngp", biased_sample=True):
         self.args = args
@@ -41,13 +45,14 @@ class ActiveLearner(object):
         Y_train = np.ascontiguousarray(Y_train, dtype=np.float64).reshape(X_train.shape[0], -1)
         n, d = X_train.shape
         acts = getattr(kernel_fn, "activations", None)
-        if (self._model is None or self._model.n_cap < n or self._model.d != d or self._model.get != self.kernel_type
+        scale = getattr(kernel_fn, "input_scale", None)
+        if (self._model is None or not _same_scale(self._model.input_scale, scale) or self._model.n_cap < n or self._model.d != d or self._model.get != self.kernel_type
                 or self._model.activations != tuple(_lib.canonical_activation(a) for a in (acts or [("relu",)] * len(kernel_fn.w_std[1:])))):
             if self._model is not None:
                 self._model.close()
             self._fitted = None
             self._model = GPModel(max(n, n_cap or n), d, kernel_fn.w_std, kernel_fn.b_std, get=self.kernel_type,
-                                  diag_reg=1e-3, ny=Y_train.shape[1], activations=acts)
+                                  diag_reg=1e-3, ny=Y_train.shape[1], activations=acts, input_scale=scale)
         # When the new training set extends the fitted one (the loop below appends the selected pool queries), only the
         # new kernel rows are built and the factor is extended (GPModel.append) instead of a full refit.
         prev = self._fitted

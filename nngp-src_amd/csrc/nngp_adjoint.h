@@ -6,12 +6,15 @@
 //   seeds of the leave-one-out loss:    1/2 (alpha_i u_j + u_i alpha_j)             and  C_ij = (A^-1 diag(bbar) A^-1)_ij
 // Everything else -- tiling, Gram staging, forward recursion, reverse sweep, the q = 0 and exact-diagonal rules, the fixed-order
 // reduction -- is one piece of code (adjoint_tile), so both objectives differentiate the same kernel.
+// With per-feature input relevances (nngp_ard.hip) the same pass also leaves the seeded adjoints at the input of Dense layer 0
+// behind (the ARD flag), from which one contraction with X gives the derivative with respect to every relevance.
 #pragma once
 #include "gp_f64.h"
 #include "f64_math.h"
 #include "trig_tab.h"
 
 #include <cmath>
+#include <vector>
 
 namespace nngp {
 
@@ -35,19 +38,33 @@ struct MllArgs {
     const double* u;      // [Np]: A^-1 abar (leave-one-out loss only)
     double* part;         // [2 ncomp][nparts]: the rank-one / rank-two half of every component, then the matrix half
     int64_t nparts;
+    // input relevances (nngp_ard.hip) only: the seeded adjoints at the input of Dense layer 0
+    double* cmat;         // [Np, ldc]: kbar of the first seed at (i, j), of the matrix seed at (j, i), for j < i
+    int64_t ldc;
+    double* qbar;         // [2][tiles per side][np]: per seed the row sums of qbar1 / column sums of qbar2, one slot per tile
+    int64_t np;
 };
 
 // NLC: room for n_dense <= NLC layers (the per-entry state lives in registers, so its size must be known at compile time).
 // LOO: the rank-two seed 1/2 (alpha_i u_j + u_i alpha_j) instead of alpha_i alpha_j.
-template <int NLC, bool LOO>
+// ARD: also keep what the reverse sweep holds once it has passed Dense layer 0 -- kbar = S_ij dK_ij/dK0_ij into cmat, and
+// qbar1 = S_ij dK_ij/dq_i, qbar2 = S_ij dK_ij/dq_j summed over the tile's columns / rows into qbar.  Tile (ti, tj) writes its row
+// part to slot tj and its column part to slot ti (a diagonal tile the sum of both), so every slot has one writer.  A diagonal
+// entry depends on q_i alone (exact diagonal), so its kbar belongs to qbar.
+template <int NLC, bool LOO, bool ARD = false>
 __device__ __forceinline__ void adjoint_tile(const MllArgs& a, const ArchDev& arch) {
     __shared__ __attribute__((aligned(16))) double sm[2 * MT * MLD];  // the two row panels, then the Gram tile [MT][MT + 1]
     __shared__ double qs[NLC][2 * MT];  // rows | columns: q at the input of Dense layer l
     __shared__ double rq[NLC][2 * MT];  // 1 / (4 pi q') with q' after Dense layer l; 0 where q' = 0 (the q = 0 rule)
     __shared__ __attribute__((aligned(16))) double tab[65 * 4];
     __shared__ double red[256];
+    // ARD: [seed][row][tc] and [seed][column][tr] -- every thread sums into slots of its own, in the order of its entries
+    __shared__ double rsum[ARD ? 2 : 1][ARD ? MT : 1][17], csum[ARD ? 2 : 1][ARD ? MT : 1][17];
     static_assert(MT * (MT + 1) <= 2 * MT * MLD, "the Gram tile aliases the panels");
     const int tid = threadIdx.x, tc = tid & 15, tr = tid >> 4;
+    if constexpr (ARD) {
+        for (int e = tid; e < 2 * MT * 17; e += 256) (&rsum[0][0][0])[e] = (&csum[0][0][0])[e] = 0.0;
+    }
     const int nd = arch.n_dense;
     const int64_t tn = (a.n + MT - 1) / MT;
     int64_t ti, tj;
@@ -182,6 +199,35 @@ __device__ __forceinline__ void adjoint_tile(const MllArgs& a, const ArchDev& ar
                 q2i *= v;
             }
         }
+        if constexpr (ARD) {
+            if (dg) {
+                rsum[0][ri][tc] += kb_a;
+                rsum[1][ri][tc] += kb_i;
+            } else {
+                a.cmat[i * a.ldc + j] = kb_a;
+                a.cmat[j * a.ldc + i] = kb_i;
+                rsum[0][ri][tc] += q1a;
+                rsum[1][ri][tc] += q1i;
+                csum[0][cj][tr] += q2a;
+                csum[1][cj][tr] += q2i;
+            }
+        }
+    }
+    if constexpr (ARD) {
+        __syncthreads();
+        const int arr = tid >> 6, r = tid & (MT - 1);  // 0, 1: row sums of seed 0, 1; 2, 3: column sums
+        const double* src = arr < 2 ? rsum[arr][r] : csum[arr - 2][r];
+        double t = 0.0;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) t += src[e];
+        red[tid] = t;
+        __syncthreads();
+        if (ti == tj) {
+            if (tid < 2 * MT) a.qbar[((int64_t)arr * tn + ti) * a.np + i0 + r] = red[tid] + red[tid + 2 * MT];
+        } else {
+            a.qbar[((int64_t)(arr & 1) * tn + (arr < 2 ? tj : ti)) * a.np + (arr < 2 ? i0 : j0) + r] = t;
+        }
+        __syncthreads();
     }
     const int ncomp = 2 * nd;
 #pragma unroll
@@ -239,7 +285,23 @@ inline void trace_dk(const ArchDev& arch, const double* sq, double dn, double* t
 
 }  // namespace nngp
 
-// The handle of include/nngp_mll.h and include/nngp_loo.h
+namespace nngp {
+// What nngp_mll_reserve_ard adds to the handle (include/nngp_ard.h); all NULL / empty on a handle without relevances
+struct ArdBuffers {
+    bool reserved = false;
+    double* xs = nullptr;     // n_cap x d: x scaled by sqrt(s), what the kernel build and the adjoint pass read
+    double* q = nullptr;      // n_cap: |xs_i|^2 / d
+    double* s = nullptr;      // d: the relevances
+    double* qbar = nullptr;   // [2][tiles per side][np_cap]: MllArgs::qbar
+    double* part = nullptr;   // [3][tiles per side][d]: per row block the contraction of either seed, and sum x_ik^2
+    double* out = nullptr;    // [3][d]: these summed over the row blocks
+    std::vector<double> host;   // out on the host
+    std::vector<double> terms;  // nngp_mll_ard_terms: both halves per feature, then tr dK/ds_k
+    bool have_terms = false;
+};
+}  // namespace nngp
+
+// The handle of include/nngp_mll.h, include/nngp_loo.h and include/nngp_ard.h
 struct nngp_mll {
     nngp::GpWorkspace w;      // part: 2 kMaxComp per tile; red: [0, 2) tr K, r; [kRed, ...) the finish kernels' sums
     double* q = nullptr;      // n_cap: |x_i|^2 / d
@@ -252,11 +314,29 @@ struct nngp_mll {
     bool have_loo_terms = false;
     double loo_terms[2 * (nngp::kMaxComp + 1) + 3 + nngp::kMaxComp] = {};
     int n_loo_terms = 0;
+    nngp::ArdBuffers ard;
 };
 
 namespace nngp {
 // nngp_mll.hip: the architecture checked for the float64 gradient paths (rc -2 naming `who`), and A = K + r I (get: NNGP_GET_NNGP,
 // or NNGP_GET_NTK for Theta + r I) in w.a with the identity on the padding; red[0] = tr K, red[1] = r
+// x, q: the inputs and their row norms (the handle's own, or the scaled copy of ArdBuffers)
 int mll_make_arch(const nngp_arch_act* arch_in, double diag_reg, const char* who, ArchDev* arch);
-int mll_build_a(nngp_mll* h, const ArchDev& arch, int get, double diag_reg, int absolute, hipStream_t s);
+int mll_build_a(nngp_mll* h, const ArchDev& arch, int get, double diag_reg, int absolute, const double* x, const double* q,
+                hipStream_t s);
+// The evaluations behind nngp_mll_evaluate / nngp_mll_loo_evaluate and their _ard forms.  rel: host, d relevances, or NULL for
+// the handle's own x (then grad_s is NULL too); grad_s: host, d values, or NULL.
+int mll_evaluate_core(nngp_mll* h, const nngp_arch_act* arch_in, double diag_reg, int absolute, double* nlml, double* grad,
+                      const double* rel, double* grad_s, const char* who, hipStream_t s);
+int loo_evaluate_core(nngp_mll* h, const nngp_arch_act* arch_in, int get, double diag_reg, int absolute, int objective, double* value,
+                      double* grad, const double* rel, double* grad_s, const char* who, hipStream_t s);
+// nngp_ard.hip.  ard_begin: checks rel, uploads it, fills ard.xs and ard.q.  launch_ard_partial: the adjoint pass with ARD set
+// (a.cmat / a.qbar filled in from the handle).  ard_contract: the contraction and its finish into ard.out, queued for the host
+// copy ard.host.  ard_finish_host (after the stream is synchronised): grad_s and the terms from ard.host; s1, s2 multiply
+// lambda tr dK / N in the two halves (alpha^T alpha, tr A^-1; or alpha^T u, tr C), loo picks -(h1 + h2) over -h1/2 + h2/2.
+int ard_begin(nngp_mll* h, const double* rel, const char* who, hipStream_t s);
+int launch_ard_partial(nngp_mll* h, MllArgs a, const ArchDev& arch, bool loo, hipStream_t s);
+int ard_contract(nngp_mll* h, hipStream_t s);
+void ard_finish_host(nngp_mll* h, const ArchDev& arch, double diag_reg, int absolute, double s1, double s2, bool loo, double* grad_s);
+void ard_free(nngp_mll* h);
 }  // namespace nngp

@@ -1,0 +1,242 @@
+// Per-feature input relevances (include/nngp_ard.h) for the NNGP evidence (nngp_mll.hip) and the leave-one-out objectives
+// (nngp_loo.hip): K_s(x, x') = K(x o sqrt(s), x' o sqrt(s)) and the derivative of either loss with respect to every s_k.
+//
+//   dL/ds_k = (1/d) [ sum_{j<i} (S o c)_ij x_ik x_jk  +  sum_i qbar_i x_ik^2 ]     per seed S
+// with (S o c)_ij and qbar_i what the reverse sweep of adjoint_tile holds once it has passed Dense layer 0: kbar, and qbar1 /
+// qbar2 summed over j / i (a diagonal entry's kbar belongs to qbar: K_ii depends on q_i alone).  The off-diagonal weight 2 of
+// the lower-triangle pass is already in them, so the strict lower triangle is all there is to contract.
+//
+//   k_ard_scale          xs = x o sqrt(s)  (s = 1: the bits of x)
+//   k_nngp_ard_partial   adjoint_tile with ARD set: the usual partials, S o c of the first seed into the lower triangle of zt
+//                        (dead at this point in both paths), of the matrix seed into the upper, and the per-tile sums of qbar
+//   k_ard_contract       the new hot path: per 64-row block I, 32 features and seed, Z_I = sum_{J <= I} (S o c)[I, J] X_J on the
+//                        float64 MFMA (v_mfma_f64_16x16x4: lane l holds A[l & 15][l >> 4] and B[l >> 4][l & 15], and D at column
+//                        l & 15, row (l >> 4) + 4 reg), then sum_{i in I} x_ik (Z_ik + qbar_i x_ik), rows in order
+//   k_ard_finish         the row blocks summed in order
+// No atomics; every slot of qbar and of the partials has one writer.
+#include "nngp_adjoint.h"
+#include "../../include/nngp_ard.h"
+
+namespace nngp {
+
+namespace {
+
+constexpr int AKC = 32;  // features per workgroup of the contraction: two 16-wide MFMA column blocks per wave
+typedef double v4d __attribute__((ext_vector_type(4)));
+
+__global__ __launch_bounds__(256) void k_ard_scale(const double* x, const double* s, int64_t total, int d, double* xs) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e < total) xs[e] = x[e] * sqrt(s[e % d]);
+}
+
+template <int NLC, bool LOO>
+__global__ __launch_bounds__(256) void k_nngp_ard_partial(MllArgs a, ArchDev arch) {
+    adjoint_tile<NLC, LOO, true>(a, arch);
+}
+
+template <bool LOO>
+int launch_partial(const MllArgs& a, const ArchDev& arch, hipStream_t s) {
+    const dim3 grid((unsigned)a.nparts), block(256);
+    if (arch.n_dense <= 2) hipLaunchKernelGGL((k_nngp_ard_partial<2, LOO>), grid, block, 0, s, a, arch);
+    else if (arch.n_dense <= 4) hipLaunchKernelGGL((k_nngp_ard_partial<4, LOO>), grid, block, 0, s, a, arch);
+    else if (arch.n_dense <= 8) hipLaunchKernelGGL((k_nngp_ard_partial<8, LOO>), grid, block, 0, s, a, arch);
+    else hipLaunchKernelGGL((k_nngp_ard_partial<NNGP_MAX_DENSE, LOO>), grid, block, 0, s, a, arch);
+    NNGP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// grid (row blocks, feature chunks, 2 seeds).  cmat: seed 0 at (i, j), seed 1 at (j, i), j < i < n; x: the raw inputs.
+// part[(seed * tn + I) * d + k]; seed 0 also writes part[(2 tn + I) * d + k] = sum_{i in I} x_ik^2.
+__global__ __launch_bounds__(256) void k_ard_contract(const double* cmat, int64_t ldc, const double* x, int64_t n, int d,
+                                                      const double* qbar, int64_t np, int64_t tn, double* part) {
+    __shared__ double ms[MT][MT + 1];
+    __shared__ double xt[MT][AKC + 1];
+    __shared__ double qb[MT];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, lr = lane & 15, lk = lane >> 4;
+    const int64_t ti = blockIdx.x, i0 = ti * MT;
+    const int k0 = blockIdx.y * AKC, seed = blockIdx.z;
+    if (tid < MT) {  // qbar of the block's rows: the tiles' slots in order
+        double t = 0.0;
+        for (int64_t sl = 0; sl < tn; ++sl) t += qbar[((int64_t)seed * tn + sl) * np + i0 + tid];
+        qb[tid] = t;
+    }
+    v4d acc[2] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
+    for (int64_t tj = 0; tj <= ti; ++tj) {
+        const int64_t j0 = tj * MT;
+        for (int e = tid; e < MT * MT; e += 256) {  // the fast index runs along memory for either seed
+            const int r = seed == 0 ? e >> 6 : e & (MT - 1), c = seed == 0 ? e & (MT - 1) : e >> 6;
+            const int64_t i = i0 + r, j = j0 + c;
+            ms[r][c] = (i < n && j < i) ? (seed == 0 ? cmat[i * ldc + j] : cmat[j * ldc + i]) : 0.0;
+        }
+        for (int e = tid; e < MT * AKC; e += 256) {
+            const int c = e / AKC, k = e % AKC;
+            const int64_t j = j0 + c;
+            xt[c][k] = (j < n && k0 + k < d) ? x[j * d + k0 + k] : 0.0;
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int kk = 0; kk < MT; kk += 4) {
+            const double av = ms[16 * wv + lr][kk + lk];
+            acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, xt[kk + lk][lr], acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, xt[kk + lk][16 + lr], acc[1], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+    for (int e = tid; e < MT * AKC; e += 256) {  // the block's own rows of x
+        const int c = e / AKC, k = e % AKC;
+        const int64_t i = i0 + c;
+        xt[c][k] = (i < n && k0 + k < d) ? x[i * d + k0 + k] : 0.0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int hb = 0; hb < 2; ++hb)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            const int r = 16 * wv + lk + 4 * reg, c = 16 * hb + lr;
+            const double xv = xt[r][c];
+            ms[r][c] = xv * (acc[hb][reg] + qb[r] * xv);
+        }
+    __syncthreads();
+    if (tid < AKC) {
+        double t = 0.0;
+        for (int r = 0; r < MT; ++r) t += ms[r][tid];
+        if (k0 + tid < d) part[((int64_t)seed * tn + ti) * d + k0 + tid] = t;
+    } else if (tid < 2 * AKC && seed == 0) {
+        const int k = tid - AKC;
+        double t = 0.0;
+        for (int r = 0; r < MT; ++r) t += xt[r][k] * xt[r][k];
+        if (k0 + k < d) part[((int64_t)2 * tn + ti) * d + k0 + k] = t;
+    }
+}
+
+// out[v * d + k] = sum over the row blocks, in order, of part[(v * tn + I) * d + k]  (v = 0, 1: the seeds; 2: sum_i x_ik^2)
+__global__ __launch_bounds__(256) void k_ard_finish(const double* part, int64_t tn, int d, double* out) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= 3 * d) return;
+    const int v = e / d, k = e % d;
+    double t = 0.0;
+    for (int64_t b = 0; b < tn; ++b) t += part[((int64_t)v * tn + b) * d + k];
+    out[e] = t;
+}
+
+}  // namespace
+
+int ard_begin(nngp_mll* h, const double* rel, const char* who, hipStream_t s) {
+    ArdBuffers& a = h->ard;
+    NNGP_REQUIRE(a.reserved, "%s: relevances need nngp_mll_reserve_ard first", who);
+    const int d = h->w.d;
+    for (int k = 0; k < d; ++k)
+        NNGP_REQUIRE(std::isfinite(rel[k]) && rel[k] >= 0.0, "%s: relevance %d must be finite and non-negative (%g)", who, k, rel[k]);
+    const int64_t total = h->w.n * d;
+    NNGP_HIP_CHECK(hipMemcpyAsync(a.s, rel, sizeof(double) * d, hipMemcpyHostToDevice, s));
+    NNGP_HIP_CHECK(hipStreamSynchronize(s));  // rel is the caller's
+    hipLaunchKernelGGL(k_ard_scale, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, h->w.x, a.s, total, d, a.xs);
+    NNGP_HIP_CHECK(hipGetLastError());
+    return launch_row_sqnorm(a.xs, h->w.n, d, a.q, s);
+}
+
+int launch_ard_partial(nngp_mll* h, MllArgs a, const ArchDev& arch, bool loo, hipStream_t s) {
+    NNGP_REQUIRE(a.nparts < 2147483647LL, "mll: gradient grid too large");
+    a.cmat = h->w.zt;
+    a.ldc = h->w.np;
+    a.qbar = h->ard.qbar;
+    a.np = h->w.np;
+    return loo ? launch_partial<true>(a, arch, s) : launch_partial<false>(a, arch, s);
+}
+
+int ard_contract(nngp_mll* h, hipStream_t s) {
+    ArdBuffers& a = h->ard;
+    const GpWorkspace& w = h->w;
+    const int64_t tn = (w.n + MT - 1) / MT;
+    const int d = w.d;
+    const dim3 grid((unsigned)tn, (unsigned)((d + AKC - 1) / AKC), 2);
+    hipLaunchKernelGGL(k_ard_contract, grid, dim3(256), 0, s, w.zt, w.np, w.x, w.n, d, a.qbar, w.np, tn, a.part);
+    hipLaunchKernelGGL(k_ard_finish, dim3((unsigned)((3 * d + 255) / 256)), dim3(256), 0, s, a.part, tn, d, a.out);
+    NNGP_HIP_CHECK(hipGetLastError());
+    NNGP_HIP_CHECK(hipMemcpyAsync(a.host.data(), a.out, sizeof(double) * 3 * d, hipMemcpyDeviceToHost, s));
+    return 0;
+}
+
+void ard_finish_host(nngp_mll* h, const ArchDev& arch, double diag_reg, int absolute, double s1, double s2, bool loo, double* grad_s) {
+    ArdBuffers& a = h->ard;
+    const int d = h->w.d, nd = arch.n_dense;
+    const double dn = (double)h->w.n, dd = (double)d;
+    double d0v0 = 1.0;  // dK_ii / dq_i: D_0 v_0 of trace_dk
+    for (int l = nd - 1; l >= 0; --l) {
+        if (l < nd - 1) d0v0 *= arch.act[l] == NNGP_ACT_ABRELU ? arch.ap[l][2] : 0.5;
+        d0v0 *= arch.w2[l];
+    }
+    for (int k = 0; k < d; ++k) {
+        const double trdk = d0v0 * a.host[2 * d + k] / dd;
+        const double ci = absolute ? 0.0 : diag_reg * (trdk / dn);
+        const double h1 = a.host[k] / dd + ci * s1, h2 = a.host[d + k] / dd + ci * s2;
+        a.terms[2 * k] = h1;
+        a.terms[2 * k + 1] = h2;
+        a.terms[2 * d + k] = trdk;
+        grad_s[k] = loo ? -(h1 + h2) : -0.5 * h1 + 0.5 * h2;
+    }
+    a.have_terms = true;
+}
+
+void ard_free(nngp_mll* h) {
+    ArdBuffers& a = h->ard;
+    dev_free(a.xs);
+    dev_free(a.q);
+    dev_free(a.s);
+    dev_free(a.qbar);
+    dev_free(a.part);
+    dev_free(a.out);
+    a.reserved = a.have_terms = false;
+}
+
+}  // namespace nngp
+
+using namespace nngp;
+
+extern "C" {
+
+int nngp_mll_reserve_ard(nngp_mll* h) {
+    NNGP_REQUIRE(h != nullptr, "mll_reserve_ard: NULL argument");
+    ArdBuffers& a = h->ard;
+    if (a.reserved) return 0;
+    const GpWorkspace& w = h->w;
+    const int64_t tn = (w.n_cap + MT - 1) / MT, d = w.d;
+    int rc = dev_alloc(&a.xs, w.n_cap * d);
+    if (rc == 0) rc = dev_alloc(&a.q, w.n_cap);
+    if (rc == 0) rc = dev_alloc(&a.s, d);
+    if (rc == 0) rc = dev_alloc(&a.qbar, 2 * tn * w.np_cap);
+    if (rc == 0) rc = dev_alloc(&a.part, 3 * tn * d);
+    if (rc == 0) rc = dev_alloc(&a.out, 3 * d);
+    if (rc != 0) {
+        ard_free(h);
+        return rc;
+    }
+    a.host.assign((size_t)(3 * d), 0.0);
+    a.terms.assign((size_t)(3 * d), 0.0);
+    a.reserved = true;
+    return 0;
+}
+
+int nngp_mll_evaluate_ard(nngp_mll* h, const nngp_arch_act* arch, const double* s, double diag_reg, int32_t absolute, double* nlml,
+                          double* grad, double* grad_s, void* stream) {
+    NNGP_REQUIRE(s != nullptr, "mll_evaluate_ard: NULL argument");
+    return mll_evaluate_core(h, arch, diag_reg, absolute, nlml, grad, s, grad_s, "mll_evaluate_ard", (hipStream_t)stream);
+}
+
+int nngp_mll_loo_evaluate_ard(nngp_mll* h, const nngp_arch_act* arch, int32_t get, const double* s, double diag_reg, int32_t absolute,
+                              int32_t objective, double* value, double* grad, double* grad_s, void* stream) {
+    NNGP_REQUIRE(s != nullptr, "mll_loo_evaluate_ard: NULL argument");
+    return loo_evaluate_core(h, arch, get, diag_reg, absolute, objective, value, grad, s, grad_s, "mll_loo_evaluate_ard",
+                             (hipStream_t)stream);
+}
+
+int nngp_mll_ard_terms(const nngp_mll* h, double* out, int32_t count) {
+    NNGP_REQUIRE(h != nullptr && out != nullptr, "mll_ard_terms: NULL argument");
+    NNGP_REQUIRE(h->ard.have_terms, "mll_ard_terms: no evaluation with grad_s yet");
+    const int n_terms = 3 * h->w.d;
+    NNGP_REQUIRE(count >= n_terms, "mll_ard_terms: count=%d, the last evaluation has %d terms", count, n_terms);
+    for (int i = 0; i < n_terms; ++i) out[i] = h->ard.terms[i];
+    return 0;
+}
+
+}  // extern "C"

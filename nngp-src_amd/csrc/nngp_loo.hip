@@ -15,6 +15,7 @@
 //   k_nngp_loo_partial   the fused adjoint pass of nngp_adjoint.h from the seeds 1/2 (alpha_i u_j + u_i alpha_j) and C_ij
 //   k_loo_finish         one workgroup, fixed order: alpha^T u, tr C, the q chain's per-layer sums, the partial vectors
 // No atomics anywhere: repeated evaluations are bit-identical.
+// The evaluation itself is loo_evaluate_core, which nngp_mll_loo_evaluate_ard (nngp_ard.hip) calls with relevances.
 #include "nngp_adjoint.h"
 #include "../../include/nngp_loo.h"
 
@@ -119,52 +120,52 @@ int loo_c_product(double* c, const double* zs, const double* ainv, int64_t np, h
 
 }  // namespace
 
-}  // namespace nngp
-
-using namespace nngp;
-
-extern "C" {
-
-int nngp_mll_loo_evaluate(nngp_mll* h, const nngp_arch_act* arch_in, int32_t get, double diag_reg, int32_t absolute,
-                          int32_t objective, double* value, double* grad, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    NNGP_REQUIRE(h != nullptr && arch_in != nullptr && value != nullptr, "mll_loo_evaluate: NULL argument");
-    NNGP_REQUIRE(h->w.n > 0, "mll_loo_evaluate: no training data (nngp_mll_set_train)");
-    NNGP_REQUIRE(get == NNGP_GET_NNGP || get == NNGP_GET_NTK, "mll_loo_evaluate: get must be NNGP_GET_NNGP or NNGP_GET_NTK (%d)", get);
-    NNGP_REQUIRE(objective == NNGP_LOO_NLPD || objective == NNGP_LOO_MSE, "mll_loo_evaluate: unknown objective %d", objective);
-    NNGP_REQUIRE(get == NNGP_GET_NNGP || grad == nullptr,
-                 "mll_loo_evaluate: no gradient for the NTK (its mean is kernel ridge regression; the ensemble posterior is not a GP "
-                 "with prior Theta)");
+int loo_evaluate_core(nngp_mll* h, const nngp_arch_act* arch_in, int get, double diag_reg, int absolute, int objective, double* value,
+                      double* grad, const double* rel, double* grad_s, const char* who, hipStream_t s) {
+    NNGP_REQUIRE(h != nullptr && arch_in != nullptr && value != nullptr, "%s: NULL argument", who);
+    NNGP_REQUIRE(h->w.n > 0, "%s: no training data (nngp_mll_set_train)", who);
+    NNGP_REQUIRE(get == NNGP_GET_NNGP || get == NNGP_GET_NTK, "%s: get must be NNGP_GET_NNGP or NNGP_GET_NTK (%d)", who, get);
+    NNGP_REQUIRE(objective == NNGP_LOO_NLPD || objective == NNGP_LOO_MSE, "%s: unknown objective %d", who, objective);
+    NNGP_REQUIRE(get == NNGP_GET_NNGP || (grad == nullptr && grad_s == nullptr),
+                 "%s: no gradient for the NTK (its mean is kernel ridge regression; the ensemble posterior is not a GP "
+                 "with prior Theta)", who);
     NNGP_REQUIRE(get == NNGP_GET_NNGP || objective == NNGP_LOO_MSE,
-                 "mll_loo_evaluate: nlpd needs a predictive variance, which the NTK's leave-one-out form does not have");
+                 "%s: nlpd needs a predictive variance, which the NTK's leave-one-out form does not have", who);
     ArchDev arch{};
-    NNGP_TRY(mll_make_arch(arch_in, diag_reg, "mll_loo_evaluate", &arch));
+    NNGP_TRY(mll_make_arch(arch_in, diag_reg, who, &arch));
     const int nd = arch.n_dense;
     GpWorkspace& w = h->w;
-    w.factored = h->have_loo_terms = false;
+    w.factored = h->have_loo_terms = h->ard.have_terms = false;
     h->loo_get = 0;
     const int64_t n = w.n, np = w.np, npc = w.np_cap;
     double* lv = h->loo;
-    const bool want = grad != nullptr;
+    const bool want = grad != nullptr || grad_s != nullptr;
+    double own_grad[kMaxComp + 1];
+    if (want && !grad) grad = own_grad;
+    if (rel) NNGP_TRY(ard_begin(h, rel, who, s));
+    const double* x = rel ? h->ard.xs : w.x;
+    const double* q = rel ? h->ard.q : h->q;
 
-    NNGP_TRY(mll_build_a(h, arch, get, diag_reg, absolute, s));
-    NNGP_TRY(factor_and_solve(&w, want ? kGpSolveInverse : kGpSolveRows, "mll_loo_evaluate", s, lv + kNegB * npc));
+    NNGP_TRY(mll_build_a(h, arch, get, diag_reg, absolute, x, q, s));
+    NNGP_TRY(factor_and_solve(&w, want ? kGpSolveInverse : kGpSolveRows, who, s, lv + kNegB * npc));
     hipLaunchKernelGGL(k_loo_point, dim3(1), dim3(256), 0, s, w.alpha, lv + kNegB * npc, w.y, n, np, (int)objective, lv + kAbar * npc,
                        lv + kBbar * npc, lv + kMean * npc, lv + kVar * npc, w.red + kRed);
     NNGP_HIP_CHECK(hipGetLastError());
     const int64_t nparts = gp_lower_tiles(n);
     if (want) {
-        NNGP_REQUIRE((np / TB) * np <= w.t_rows * TB, "mll_loo_evaluate: solve scratch too small for the symmetric product");
+        NNGP_REQUIRE((np / TB) * np <= w.t_rows * TB, "%s: solve scratch too small for the symmetric product", who);
         NNGP_TRY(launch_symv_f64(w.ainv, np, n, lv + kAbar * npc, lv + kU * npc, 0.0, w.t, np, s));
         hipLaunchKernelGGL(k_loo_scale_cols, dim3((unsigned)((np + 255) / 256), (unsigned)np), dim3(256), 0, s, w.ainv, lv + kBbar * npc,
                            w.zt, np, np);
         NNGP_HIP_CHECK(hipGetLastError());
         NNGP_TRY(loo_c_product(w.a, w.zt, w.ainv, np, s));  // over the factor
-        MllArgs ma{w.x, h->q, n, w.d, w.a, np, w.alpha, lv + kU * npc, w.part, nparts};
-        NNGP_TRY(launch_loo_partial(ma, arch, s));
-        hipLaunchKernelGGL(k_loo_finish, dim3(1), dim3(256), 0, s, w.a, np, n, w.alpha, lv + kU * npc, w.part, nparts, h->q, arch,
+        MllArgs ma{x, q, n, w.d, w.a, np, w.alpha, lv + kU * npc, w.part, nparts};
+        if (grad_s) NNGP_TRY(launch_ard_partial(h, ma, arch, true, s));  // A^-1 diag(bbar) is dead once C exists
+        else NNGP_TRY(launch_loo_partial(ma, arch, s));
+        hipLaunchKernelGGL(k_loo_finish, dim3(1), dim3(256), 0, s, w.a, np, n, w.alpha, lv + kU * npc, w.part, nparts, q, arch,
                            w.red + kRed);
         NNGP_HIP_CHECK(hipGetLastError());
+        if (grad_s) NNGP_TRY(ard_contract(h, s));
     }
     double r[kRedLen];
     NNGP_HIP_CHECK(hipMemcpyAsync(r, w.red, sizeof(r), hipMemcpyDeviceToHost, s));
@@ -205,7 +206,20 @@ int nngp_mll_loo_evaluate(nngp_mll* h, const nngp_arch_act* arch_in, int32_t get
     for (int p = 0; p < ncomp; ++p) tail[3 + p] = trdk[p];
     h->n_loo_terms = 2 * (ncomp + 1) + 3 + ncomp;
     h->have_loo_terms = true;
+    if (grad_s) ard_finish_host(h, arch, diag_reg, absolute, au, tr_c, true, grad_s);
     return 0;
+}
+
+}  // namespace nngp
+
+using namespace nngp;
+
+extern "C" {
+
+int nngp_mll_loo_evaluate(nngp_mll* h, const nngp_arch_act* arch_in, int32_t get, double diag_reg, int32_t absolute,
+                          int32_t objective, double* value, double* grad, void* stream) {
+    return loo_evaluate_core(h, arch_in, get, diag_reg, absolute, objective, value, grad, nullptr, nullptr, "mll_loo_evaluate",
+                             (hipStream_t)stream);
 }
 
 int nngp_mll_loo_predictions(const nngp_mll* h, double* mean, double* var, void* stream) {

@@ -16,6 +16,8 @@
 //   k_mll_finish         one workgroup, fixed order: the partial vectors, sum log L_ii, |w|^2, alpha^T alpha, tr A^-1 and the
 //                        per-layer sums of the diagonal's q chain (tr dK/dtheta follows from them in closed form)
 // No atomics anywhere: repeated evaluations are bit-identical.
+// The evaluation itself is mll_evaluate_core: nngp_mll_evaluate calls it without relevances, nngp_mll_evaluate_ard (nngp_ard.hip) with
+// them -- one sequence, so that unit relevances give the bits of the entry point without.
 #include "nngp_adjoint.h"
 
 #include <vector>
@@ -98,12 +100,13 @@ int mll_make_arch(const nngp_arch_act* arch_in, double diag_reg, const char* who
 }
 
 // K (or Theta) by the kernel build (per-layer recursion: no_comp), the padding the identity, r on the diagonal
-int mll_build_a(nngp_mll* h, const ArchDev& arch, int get, double diag_reg, int absolute, hipStream_t s) {
+int mll_build_a(nngp_mll* h, const ArchDev& arch, int get, double diag_reg, int absolute, const double* x, const double* q,
+                hipStream_t s) {
     GpWorkspace& w = h->w;
     const int64_t n = w.n, np = w.np;
     BuildArgs b{};
-    b.x1 = b.x2 = w.x;
-    b.q1 = b.q2 = h->q;
+    b.x1 = b.x2 = x;
+    b.q1 = b.q2 = q;
     b.n1 = b.n2 = n;
     b.d = w.d;
     b.row_begin = 0;
@@ -120,82 +123,34 @@ int mll_build_a(nngp_mll* h, const ArchDev& arch, int get, double diag_reg, int 
     return 0;
 }
 
-}  // namespace nngp
-
-using namespace nngp;
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// C ABI (include/nngp_mll.h)
-
-static void mll_free(nngp_mll* h) {
-    dev_free(h->q);
-    dev_free(h->loo);
-    ws_free(&h->w);
-}
-
-extern "C" {
-
-int nngp_mll_create(nngp_mll** out, int64_t n_cap, int32_t d) {
-    NNGP_REQUIRE(out != nullptr && n_cap > 0 && d >= 1, "mll_create: bad arguments (n_cap=%lld, d=%d)", (long long)n_cap, d);
-    *out = nullptr;
-    nngp_mll* h = new (std::nothrow) nngp_mll();
-    NNGP_REQUIRE(h != nullptr, "mll_create: out of host memory");
-    // solve scratch: Np x 128 for the triangular solves; (Np / 128) x Np for the symmetric product u = A^-1 abar of the
-    // leave-one-out gradient (launch_symv_f64's partial rows), whichever is larger
-    const int64_t np_cap = round_up(n_cap, TB), blocks = np_cap / TB;
-    int rc = dev_alloc(&h->q, n_cap);
-    if (rc == 0) rc = dev_alloc(&h->loo, kLooVec * np_cap);
-    if (rc == 0) rc = ws_alloc(&h->w, n_cap, d, 2 * kMaxComp, kRedLen, blocks * blocks > np_cap ? blocks * blocks : np_cap);
-    if (rc != 0) {
-        mll_free(h);
-        delete h;
-        return rc;
-    }
-    *out = h;
-    return 0;
-}
-
-int nngp_mll_destroy(nngp_mll* h) {
-    if (h == nullptr) return 0;
-    (void)hipDeviceSynchronize();
-    mll_free(h);
-    delete h;
-    return 0;
-}
-
-int nngp_mll_set_train(nngp_mll* h, const double* x, const double* y, int64_t n, int32_t ny, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    NNGP_REQUIRE(h != nullptr && x != nullptr && y != nullptr, "mll_set_train: NULL argument");
-    NNGP_REQUIRE(ny == 1, "mll_set_train: the marginal likelihood takes one output column (ny=%d)", ny);
-    NNGP_REQUIRE(n >= 1 && n <= h->w.n_cap, "mll_set_train: n=%lld outside [1, n_cap=%lld]", (long long)n, (long long)h->w.n_cap);
-    h->have_terms = h->have_loo_terms = false;
-    h->loo_get = 0;
-    NNGP_TRY(launch_row_sqnorm(x, n, h->w.d, h->q, s));  // from the caller's x: ws_set_train's synchronise covers it
-    return ws_set_train(&h->w, x, y, hipMemcpyDeviceToDevice, n, s);
-}
-
-int nngp_mll_evaluate(nngp_mll* h, const nngp_arch_act* arch_in, double diag_reg, int32_t absolute, double* nlml, double* grad,
-                      void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    NNGP_REQUIRE(h != nullptr && arch_in != nullptr && nlml != nullptr, "mll_evaluate: NULL argument");
-    NNGP_REQUIRE(h->w.n > 0, "mll_evaluate: no training data (nngp_mll_set_train)");
+int mll_evaluate_core(nngp_mll* h, const nngp_arch_act* arch_in, double diag_reg, int absolute, double* nlml, double* grad,
+                      const double* rel, double* grad_s, const char* who, hipStream_t s) {
+    NNGP_REQUIRE(h != nullptr && arch_in != nullptr && nlml != nullptr, "%s: NULL argument", who);
+    NNGP_REQUIRE(h->w.n > 0, "%s: no training data (nngp_mll_set_train)", who);
     ArchDev arch{};
-    NNGP_TRY(mll_make_arch(arch_in, diag_reg, "mll_evaluate", &arch));
+    NNGP_TRY(mll_make_arch(arch_in, diag_reg, who, &arch));
     const int nd = arch.n_dense;
     GpWorkspace& w = h->w;
-    w.factored = h->have_terms = false;
+    w.factored = h->have_terms = h->ard.have_terms = false;
     const int64_t n = w.n, np = w.np;
-    NNGP_TRY(mll_build_a(h, arch, NNGP_GET_NNGP, diag_reg, absolute, s));
-    const bool want = grad != nullptr;
-    NNGP_TRY(factor_and_solve(&w, want, "mll_evaluate", s));
+    if (rel) NNGP_TRY(ard_begin(h, rel, who, s));
+    const double* x = rel ? h->ard.xs : w.x;
+    const double* q = rel ? h->ard.q : h->q;
+    NNGP_TRY(mll_build_a(h, arch, NNGP_GET_NNGP, diag_reg, absolute, x, q, s));
+    const bool want = grad != nullptr || grad_s != nullptr;
+    double own_grad[kMaxComp + 1];
+    if (want && !grad) grad = own_grad;
+    NNGP_TRY(factor_and_solve(&w, want, who, s));
     const int64_t nparts = gp_lower_tiles(n);
     if (want) {
-        MllArgs ma{w.x, h->q, n, w.d, w.ainv, np, w.alpha, nullptr, w.part, nparts};
-        NNGP_TRY(launch_mll_partial(ma, arch, s));
+        MllArgs ma{x, q, n, w.d, w.ainv, np, w.alpha, nullptr, w.part, nparts};
+        if (grad_s) NNGP_TRY(launch_ard_partial(h, ma, arch, false, s));  // L^-T is dead: the seeded adjoints go over it
+        else NNGP_TRY(launch_mll_partial(ma, arch, s));
     }
     hipLaunchKernelGGL(k_mll_finish, dim3(1), dim3(256), 0, s, w.a, np, n, w.wrow, want ? w.part : nullptr, nparts,
-                       want ? w.alpha : nullptr, w.ainv, h->q, arch, w.red + kRed);
+                       want ? w.alpha : nullptr, w.ainv, q, arch, w.red + kRed);
     NNGP_HIP_CHECK(hipGetLastError());
+    if (grad_s) NNGP_TRY(ard_contract(h, s));
     double r[kRedLen];
     NNGP_HIP_CHECK(hipMemcpyAsync(r, w.red, sizeof(r), hipMemcpyDeviceToHost, s));
     NNGP_HIP_CHECK(hipStreamSynchronize(s));
@@ -237,7 +192,68 @@ int nngp_mll_evaluate(nngp_mll* h, const nngp_arch_act* arch_in, double diag_reg
     for (int p = 0; p < ncomp; ++p) tail[5 + p] = trdk[p];
     h->n_terms = 2 * (ncomp + 1) + 5 + ncomp;
     h->have_terms = true;
+    if (grad_s) ard_finish_host(h, arch, diag_reg, absolute, aa, tr_ainv, false, grad_s);
     return 0;
+}
+
+}  // namespace nngp
+
+using namespace nngp;
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// C ABI (include/nngp_mll.h)
+
+static void mll_free(nngp_mll* h) {
+    ard_free(h);
+    dev_free(h->q);
+    dev_free(h->loo);
+    ws_free(&h->w);
+}
+
+extern "C" {
+
+int nngp_mll_create(nngp_mll** out, int64_t n_cap, int32_t d) {
+    NNGP_REQUIRE(out != nullptr && n_cap > 0 && d >= 1, "mll_create: bad arguments (n_cap=%lld, d=%d)", (long long)n_cap, d);
+    *out = nullptr;
+    nngp_mll* h = new (std::nothrow) nngp_mll();
+    NNGP_REQUIRE(h != nullptr, "mll_create: out of host memory");
+    // solve scratch: Np x 128 for the triangular solves; (Np / 128) x Np for the symmetric product u = A^-1 abar of the
+    // leave-one-out gradient (launch_symv_f64's partial rows), whichever is larger
+    const int64_t np_cap = round_up(n_cap, TB), blocks = np_cap / TB;
+    int rc = dev_alloc(&h->q, n_cap);
+    if (rc == 0) rc = dev_alloc(&h->loo, kLooVec * np_cap);
+    if (rc == 0) rc = ws_alloc(&h->w, n_cap, d, 2 * kMaxComp, kRedLen, blocks * blocks > np_cap ? blocks * blocks : np_cap);
+    if (rc != 0) {
+        mll_free(h);
+        delete h;
+        return rc;
+    }
+    *out = h;
+    return 0;
+}
+
+int nngp_mll_destroy(nngp_mll* h) {
+    if (h == nullptr) return 0;
+    (void)hipDeviceSynchronize();
+    mll_free(h);
+    delete h;
+    return 0;
+}
+
+int nngp_mll_set_train(nngp_mll* h, const double* x, const double* y, int64_t n, int32_t ny, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    NNGP_REQUIRE(h != nullptr && x != nullptr && y != nullptr, "mll_set_train: NULL argument");
+    NNGP_REQUIRE(ny == 1, "mll_set_train: the marginal likelihood takes one output column (ny=%d)", ny);
+    NNGP_REQUIRE(n >= 1 && n <= h->w.n_cap, "mll_set_train: n=%lld outside [1, n_cap=%lld]", (long long)n, (long long)h->w.n_cap);
+    h->have_terms = h->have_loo_terms = h->ard.have_terms = false;
+    h->loo_get = 0;
+    NNGP_TRY(launch_row_sqnorm(x, n, h->w.d, h->q, s));  // from the caller's x: ws_set_train's synchronise covers it
+    return ws_set_train(&h->w, x, y, hipMemcpyDeviceToDevice, n, s);
+}
+
+int nngp_mll_evaluate(nngp_mll* h, const nngp_arch_act* arch_in, double diag_reg, int32_t absolute, double* nlml, double* grad,
+                      void* stream) {
+    return mll_evaluate_core(h, arch_in, diag_reg, absolute, nlml, grad, nullptr, nullptr, "mll_evaluate", (hipStream_t)stream);
 }
 
 int nngp_mll_terms(const nngp_mll* h, double* out, int32_t count) {

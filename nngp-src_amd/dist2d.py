@@ -127,10 +127,12 @@ class _Comm:
 class HipOps:
     """The tile arithmetic on the MI355X, through the C ABI (include/nngp_hip.h).  Raises without the library or a GPU."""
 
-    def __init__(self, w_std, b_std, get: str = "nngp", activations=None):
+    def __init__(self, w_std, b_std, get: str = "nngp", activations=None, input_scale=None):
         import ctypes
         import torch
         from . import _lib
+        if input_scale is not None:
+            raise NotImplementedError("grid2d does not take an input_scale (per-feature relevances are single-GPU)")
         if not _lib.all_relu(activations):  # its tile operations take the ReLU architecture only
             raise NotImplementedError("grid2d supports Dense,(Relu,Dense)* networks only, got activations %r" % (activations,))
         self._lib, self._ct, self.torch = _lib, ctypes, torch

@@ -21,7 +21,8 @@ import numpy as np
 
 from . import _lib
 from .gp import F64Handle, train_hyperparameters
-from .mll import _Params, _arch_of, _grad_dict, _train_arrays, rebuild_kernel_fn
+from .mll import (_Params, _arch_of, _ard_terms, _relevance_arg, _reserve_ard, _train_arrays, rebuild_kernel_fn,
+                  evaluate_once, finish_kernel_fn, relevance_groups, relevance_of, split_input_scale, tune_loop)
 
 OBJECTIVES = {"nlpd": _lib.LOO_NLPD, "mse": _lib.LOO_MSE}
 _GET = {"nngp": _lib.GET_NNGP, "ntk": _lib.GET_NTK}
@@ -51,27 +52,46 @@ class LeaveOneOut(F64Handle):
 
     _prefix = "nngp_mll_"
 
-    def __init__(self, n_cap: int, d: int, objective="nlpd", get="nngp"):
+    def __init__(self, n_cap: int, d: int, objective="nlpd", get="nngp", ard: bool = False):
         if objective not in OBJECTIVES or get not in _GET or (get == "ntk" and objective == "nlpd"):
             raise ValueError("objective must be 'nlpd' or 'mse' and get 'nngp' or 'ntk' ('ntk' has no nlpd)")
         super().__init__(d, int(n_cap), int(d))
         self.objective, self.get = objective, get
         self.n_dense = 0
+        if ard:
+            self.reserve_ard()
 
-    def evaluate(self, kernel_fn_or_params, diag_reg=1e-3, absolute=False, with_grad=True, objective=None, get=None):
+    reserve_ard = _reserve_ard
+    _relevance = _relevance_arg
+    ard_terms = _ard_terms
+
+    def evaluate(self, kernel_fn_or_params, diag_reg=1e-3, absolute=False, with_grad=True, objective=None, get=None,
+                 relevance=None):
         """(value, grad) of the objective at the architecture of ``kernel_fn_or_params``; grad as in
-        mll.NNGPMarginalLikelihood.evaluate, None without ``with_grad``."""
+        mll.NNGPMarginalLikelihood.evaluate, None without ``with_grad``.  With ``relevance`` (d values >= 0, handle made with
+        ``ard=True``): ``(value, grad, grad_s)`` as there."""
         objective, get = objective or self.objective, get or self.get
         w, b, acts = check_supported(kernel_fn_or_params, get, objective, with_grad)
         arch = _lib.make_arch_act(w, b, acts)
         val = ctypes.c_double()
         g = (ctypes.c_double * (2 * len(w) + 1))()
-        self._check(self.lib.nngp_mll_loo_evaluate(self._h, ctypes.byref(arch), _GET[get], float(diag_reg), int(bool(absolute)),
-                                                   OBJECTIVES[objective], ctypes.byref(val), g if with_grad else None,
-                                                   _lib.stream_ptr()))
+        if relevance is None:
+            self._check(self.lib.nngp_mll_loo_evaluate(self._h, ctypes.byref(arch), _GET[get], float(diag_reg), int(bool(absolute)),
+                                                       OBJECTIVES[objective], ctypes.byref(val), g if with_grad else None,
+                                                       _lib.stream_ptr()))
+        else:
+            s = self._relevance(relevance)
+            gs = (ctypes.c_double * self.d)()
+            self._check(self.lib.nngp_mll_loo_evaluate_ard(self._h, ctypes.byref(arch), _GET[get], s, float(diag_reg),
+                                                           int(bool(absolute)), OBJECTIVES[objective], ctypes.byref(val),
+                                                           g if with_grad else None, gs if with_grad else None,
+                                                           _lib.stream_ptr()))
         self.n_dense = len(w)
         self._last_get = get
-        return val.value, (np.array(g[:], dtype=np.float64) if with_grad else None)
+        grad = np.array(g[:], dtype=np.float64) if with_grad else None
+        if relevance is None:
+            return val.value, grad
+        return val.value, grad, (np.array(gs[:], dtype=np.float64) if with_grad else None)
 
     def predictions(self):
         """(mean, var) of the last evaluation, numpy [n]; var is None after an NTK evaluation."""
@@ -101,10 +121,11 @@ def loo_predict(kernel_fn, x_train, y_train, diag_reg=1e-3, diag_reg_absolute_sc
     with Theta, var None."""
     check_supported(kernel_fn, get, "mse", False)
     x, y = _train_arrays(x_train, y_train)
-    m = LeaveOneOut(x.shape[0], x.shape[1], "mse", get)
+    rel = relevance_of(kernel_fn, x.shape[1])
+    m = LeaveOneOut(x.shape[0], x.shape[1], "mse", get, ard=rel is not None)
     try:
         m.set_train(x, y)
-        m.evaluate(kernel_fn, diag_reg, diag_reg_absolute_scale, with_grad=False)
+        m.evaluate(kernel_fn, diag_reg, diag_reg_absolute_scale, with_grad=False, relevance=rel)
         return m.predictions()
     finally:
         m.close()
@@ -114,38 +135,32 @@ def loo_objective(kernel_fn, x_train, y_train, diag_reg=1e-3, diag_reg_absolute_
                   get="nngp"):
     """The LOO objective (``'nlpd'`` or ``'mse'``, per-query means) of ``kernel_fn`` on (x_train, y_train); with ``with_grad``
     also ``{'w_std2': [...], 'b_std2': [...], 'diag_reg': g}`` as mll.marginal_likelihood returns it."""
-    w, _, _ = check_supported(kernel_fn, get, objective, with_grad)
+    check_supported(kernel_fn, get, objective, with_grad)
     x, y = _train_arrays(x_train, y_train)
-    m = LeaveOneOut(x.shape[0], x.shape[1], objective, get)
-    try:
-        m.set_train(x, y)
-        val, g = m.evaluate(kernel_fn, diag_reg, diag_reg_absolute_scale, with_grad)
-    finally:
-        m.close()
-    return (val, _grad_dict(g, len(w))) if with_grad else val
+    val, gd = evaluate_once(LeaveOneOut(x.shape[0], x.shape[1], objective, get), kernel_fn, x, y, diag_reg,
+                            diag_reg_absolute_scale, with_grad)
+    return (val, gd) if with_grad else val
 
 
 def tune_hyperparameters(kernel_fn, x_train, y_train, diag_reg=1e-3, diag_reg_absolute_scale=False, steps=50, lr=0.05,
-                         b_std_init=None, min_diag_reg=1e-6, report=print, evaluator=None, objective="nlpd"):
+                         b_std_init=None, min_diag_reg=1e-6, report=print, evaluator=None, objective="nlpd", ard=False,
+                         ard_groups=None, relevance_init=None):
     """mll.tune_hyperparameters with a leave-one-out objective in place of the NLML: the same parameters (log sigma_w,l^2,
-    log sigma_b,l^2 of the free biases, log lambda), the same update rule (gp.train_hyperparameters) and the same return value
-    ``(kernel_fn_tuned, diag_reg_tuned, history)``.  Reports ``"Step: %d, LOO %s: %f"`` after each step.  ``evaluator``: an
-    object with ``evaluate(params, diag_reg, absolute, with_grad)`` to use instead of the GPU."""
+    log sigma_b,l^2 of the free biases, log lambda and, with ``ard``, log s_k), the same update rule
+    (gp.train_hyperparameters) and the same return value ``(kernel_fn_tuned, diag_reg_tuned, history)``.  Reports
+    ``"Step: %d, LOO %s: %f"`` after each step.  ``evaluator``: an object with ``evaluate(params, diag_reg, absolute,
+    with_grad)`` to use instead of the GPU."""
     w0, b0, acts = check_supported(kernel_fn, "nngp", objective, True)
     x, y = _train_arrays(x_train, y_train)
-    params = _Params(w0, b0, diag_reg, b_std_init, min_diag_reg)
+    x, fixed_scale, relevance_init = split_input_scale(kernel_fn, x, ard, relevance_init)
+    index = relevance_groups(ard_groups, x.shape[1])[0] if ard else None
+    params = _Params(w0, b0, diag_reg, b_std_init, min_diag_reg, index, relevance_init)
     own = evaluator is None
-    ev = LeaveOneOut(x.shape[0], x.shape[1], objective).set_train(x, y) if own else evaluator
+    ev = LeaveOneOut(x.shape[0], x.shape[1], objective, ard=bool(ard)).set_train(x, y) if own else evaluator
     try:
-        def evaluate(raw, with_grad):
-            w, b, lam, _ = params.unpack(raw)
-            val, g = ev.evaluate((w, b, acts), lam, diag_reg_absolute_scale, with_grad)
-            return val, (params.grad_raw(g, raw) if with_grad else None)
-
-        raw, history = train_hyperparameters(evaluate, params.raw0, steps=steps, lr=lr, report=report,
-                                             label="LOO %s" % objective)
+        raw, history = tune_loop(params, ev, acts, diag_reg_absolute_scale, steps, lr, report, "LOO %s" % objective)
     finally:
         if own:
             ev.close()
     w, b, lam, _ = params.unpack(raw)
-    return rebuild_kernel_fn(w, b, acts), lam, history
+    return finish_kernel_fn(rebuild_kernel_fn(w, b, acts, params.relevance(raw)), fixed_scale), lam, history

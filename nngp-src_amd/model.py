@@ -21,9 +21,15 @@ _COV = {False: _lib.COV_NONE, None: _lib.COV_NONE, "none": _lib.COV_NONE, "diag"
 class GPModel:
     def __init__(self, n_cap: int, d: int, w_std, b_std, get: str = "nngp", diag_reg: float = 1e-3,
                  diag_reg_absolute_scale: bool = False, ny: int = 1, m_cap: int = 0, knobs: bool = False,
-                 activations=None):
+                 activations=None, input_scale=None):
         """activations: one per hidden layer, as ``stax.KernelFn.activations`` (None: all ReLU).  An all-ReLU model is
-        created through nngp_model_create, any other through nngp_model_create_act."""
+        created through nngp_model_create, any other through nngp_model_create_act.  input_scale: None, or d values >= 0 that
+        multiply the features of every X that enters (fit, set_train, append, predict, pool scoring) on the device, as
+        ``stax.KernelFn.input_scale`` does for the kernel."""
+        from .stax import check_input_scale
+        self.input_scale = check_input_scale(input_scale)
+        if self.input_scale is not None and self.input_scale.shape[0] != int(d):
+            raise ValueError("input_scale has %d values, the model has d = %d" % (self.input_scale.shape[0], int(d)))
         if get not in _GET:
             raise ValueError("get must be 'nngp' or 'ntk', got %r" % (get,))
         self.lib = _lib.load(knobs)  # knobs=True: the timing-knob build (A/B tests and scripts/ only)
@@ -81,8 +87,14 @@ class GPModel:
         if int(xd.shape[0]) > self.n_cap or xd.shape[0] == 0:
             raise ValueError("x_train has %d rows; the model was created for 1..%d" % (xd.shape[0], self.n_cap))
         self.n = int(xd.shape[0])
-        self._keep = [xd, yd]
-        self._check(self.lib.nngp_model_set_train(self.handle, _lib.ptr(xd), _lib.ptr(yd), self.n, _lib.stream_ptr()))
+        xs = self._scaled(xd)
+        self._keep = [xd, yd]  # what save() writes: the rows as they came in
+        self._keep_scaled = xs
+        self._check(self.lib.nngp_model_set_train(self.handle, _lib.ptr(xs), _lib.ptr(yd), self.n, _lib.stream_ptr()))
+
+    def _scaled(self, xd):
+        from .stax import apply_input_scale
+        return apply_input_scale(self.input_scale, xd)
 
     def append(self, x_new, y_new, solve: bool = True):
         """Add training rows to a fitted model: their kernel rows are built and the factor is extended in place
@@ -96,8 +108,11 @@ class GPModel:
             return self
         if self.n + b > self.n_cap:
             raise ValueError("append: %d + %d rows exceed the capacity %d" % (self.n, b, self.n_cap))
-        self._check(self.lib.nngp_model_append(self.handle, _lib.ptr(xd), _lib.ptr(yd), b, _lib.stream_ptr()))
+        xs = self._scaled(xd)
+        self._check(self.lib.nngp_model_append(self.handle, _lib.ptr(xs), _lib.ptr(yd), b, _lib.stream_ptr()))
         import torch
+        if xs is not xd:
+            torch.cuda.current_stream().synchronize()  # xs goes out of scope below
         self._keep = [torch.cat([self._keep[0], xd]), torch.cat([self._keep[1], yd])]  # what save() writes
         self.n += b
         if solve:
@@ -212,6 +227,8 @@ class GPModel:
         b = np.array([self.arch.b_std[i] for i in range(self.arch.n_dense)])
         info = self.info()
         extra = {}
+        if self.input_scale is not None:  # optional field of either version; a file without it loads as before
+            extra["input_scale"] = np.array(self.input_scale)
         if not self.all_relu:  # v2: the activations as (code, a, b, c) rows; a ReLU model keeps writing v1
             codes = {"relu": _lib.ACT_RELU, "abrelu": _lib.ACT_ABRELU, "erf": _lib.ACT_ERF}
             extra["activations"] = np.array([[codes[a[0]]] + list(a[1:]) + [0.0] * (4 - len(a)) for a in self.activations],
@@ -242,7 +259,7 @@ class GPModel:
         x, y = z["x"], z["y"]
         model = cls(max(int(z["n_cap"]), x.shape[0]), x.shape[1], z["w_std"].tolist(), z["b_std"].tolist(), get=str(z["get"]),
                     diag_reg=float(z["diag_reg"]), diag_reg_absolute_scale=bool(z["absolute"]), ny=y.shape[1], m_cap=m_cap,
-                    activations=acts)
+                    activations=acts, input_scale=(z["input_scale"] if "input_scale" in z.files else None))
         model.fit(x, y)
         if check:
             a, a0 = model.alpha().cpu().numpy(), z["alpha"]
@@ -330,6 +347,7 @@ class GPModel:
             if xt.ndim != 2 or xt.shape[1] != self.d:
                 raise ValueError("x_test must be [M, %d], got %s" % (self.d, tuple(xt.shape)))
             m = int(xt.shape[0])
+            xt = self._scaled(xt)
         mean = torch.empty((m, self.ny), dtype=torch.float64, device=self.device)
         out = None
         if mode == _lib.COV_DIAG:

@@ -32,10 +32,12 @@ class HipRowOps:
     """The per-rank arithmetic of the row-sharded layout on one MI355X through the C ABI.  Raises without the library or a GPU."""
 
     def __init__(self, n: int, d: int, w_std, b_std, diag_reg: float = 1e-3, diag_reg_absolute_scale: bool = False, world: int = 1,
-                 activations=None):
+                 activations=None, input_scale=None):
         import ctypes
         import torch
         from . import _lib
+        if input_scale is not None:
+            raise NotImplementedError("shard32 does not take an input_scale (per-feature relevances are single-GPU)")
         if not _lib.all_relu(activations):  # its row operations take the ReLU architecture only
             raise NotImplementedError("shard32 supports Dense,(Relu,Dense)* networks only, got activations %r" % (activations,))
         from .model import GPModel

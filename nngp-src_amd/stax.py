@@ -69,10 +69,34 @@ def _phi(spec, h):
     return spec[1] * torch.special.erf(torch.from_numpy(spec[2] * h)).numpy() + spec[3]
 
 
+def check_input_scale(scale):
+    """None, or the scale as a float64 vector of finite values >= 0."""
+    if scale is None:
+        return None
+    s = np.array(scale, dtype=np.float64)
+    if s.ndim != 1 or s.shape[0] < 1 or not np.all(np.isfinite(s)) or np.any(s < 0.0):
+        raise ValueError("input_scale must be one finite value >= 0 per input feature")
+    s.setflags(write=False)
+    return s
+
+
+def apply_input_scale(scale, xd):
+    """xd [n, d] (device float64, or None) times the scale, feature by feature, on xd's device."""
+    if scale is None or xd is None:
+        return xd
+    import torch
+    if int(xd.shape[1]) != scale.shape[0]:
+        raise ValueError("input_scale has %d values, x has %d features" % (scale.shape[0], int(xd.shape[1])))
+    return xd * torch.tensor(scale, dtype=torch.float64, device=xd.device)
+
+
 class KernelFn:
     """kernel_fn(x1, x2=None, get=None): closed-form kernel of Dense,(act,Dense)* on the GPU."""
 
-    def __init__(self, w_std, b_std, activations=None):
+    def __init__(self, w_std, b_std, activations=None, input_scale=None):
+        """input_scale: None or d values >= 0 that multiply the features of x1 and x2 on the device before the build --
+        sqrt of the relevances of include/nngp_ard.h (with_input_scale returns a copy that carries them)."""
+        self.input_scale = check_input_scale(input_scale)
         self.w_std = tuple(float(w) for w in w_std)
         self.b_std = tuple(float(b) for b in b_std)
         self.n_relu = len(self.w_std) - 1  # hidden layers (the name is the all-ReLU one)
@@ -82,6 +106,10 @@ class KernelFn:
         # per hidden layer: ("relu",), ("abrelu", a, b) or ("erf", a, b, c); ABRelu(0, 1) is stored as ("relu",)
         self.activations = tuple(_lib.canonical_activation(a) for a in acts)
         self.all_relu = _lib.all_relu(self.activations)
+
+    def with_input_scale(self, scale):
+        """A copy of this kernel_fn with ``input_scale = scale`` (None: without one)."""
+        return KernelFn(self.w_std, self.b_std, self.activations, scale)
 
     def _arch(self):
         if self.all_relu:
@@ -104,6 +132,8 @@ class KernelFn:
             raise ValueError("x2 must be [N2, d] with the same d as x1")
         n1, d = int(x1d.shape[0]), int(x1d.shape[1])
         n2 = n1 if x2d is None else int(x2d.shape[0])
+        if self.input_scale is not None:
+            x1d, x2d = apply_input_scale(self.input_scale, x1d), apply_input_scale(self.input_scale, x2d)
         r0, r1 = (0, n1) if rows is None else (int(rows[0]), int(rows[1]))
         outs = {g: torch.empty((n1, n2), dtype=torch.float64, device=dev) for g in set(gets)}
         if n1 > 0 and n2 > 0 and r1 > r0:

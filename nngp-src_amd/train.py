@@ -126,14 +126,20 @@ def tune_kernel_fn(args, X_train, Y_train):
     from . import loo, mll
     _, _, kernel_fn = kernel_fn_from_args(args)
     objective = getattr(args, "tune_objective", "mll")
+    ard = {}
+    if getattr(args, "tune_ard", False):  # --tune_ard: one relevance per input feature joins the tuned values (nngp_ard.h)
+        groups = getattr(args, "ard_groups", "none")
+        ard = {"ard": True, "ard_groups": None if groups == "none" else groups}
     if objective == "mll":
         kernel_fn, diag_reg, _ = mll.tune_hyperparameters(kernel_fn, X_train, Y_train, diag_reg=1e-3, steps=args.tune_hyper,
-                                                          lr=args.tune_lr, b_std_init=args.b_std_init)
+                                                          lr=args.tune_lr, b_std_init=args.b_std_init, **ard)
     else:
         kernel_fn, diag_reg, _ = loo.tune_hyperparameters(kernel_fn, X_train, Y_train, diag_reg=1e-3, steps=args.tune_hyper,
                                                           lr=args.tune_lr, b_std_init=args.b_std_init,
-                                                          objective=objective[len("loo_"):])
+                                                          objective=objective[len("loo_"):], **ard)
     print("Tuned W_std={} b_std={} diag_reg={}".format(list(kernel_fn.w_std), list(kernel_fn.b_std), diag_reg))
+    if ard:
+        print("Tuned relevances={}".format([float(v) for v in kernel_fn.input_scale ** 2]))
     return kernel_fn, diag_reg
 
 
@@ -186,6 +192,10 @@ def make_parser():
                         help="what --tune_hyper minimises: the negative log marginal likelihood, or the leave-one-out nlpd / mse")
     parser.add_argument("--loo", action='store_true',
                         help="after the fit, also print the leave-one-out error and q-error profile over the training split (nngp, ntk)")
+    parser.add_argument("--tune_ard", action='store_true',
+                        help="with --tune_hyper: also tune one relevance per input feature (W_std of the first layer is then fixed)")
+    parser.add_argument("--ard_groups", type=str, default="none", choices=("none", "pairs"),
+                        help="--tune_ard: 'pairs' ties features 2i and 2i+1, the two ends of a column's range")
     parser.add_argument("--tune_lr", type=float, default=0.05, help="step size of --tune_hyper")
     parser.add_argument("--b_std_init", type=float, default=None, help="start of b_std for layers with b_std = 0 (--tune_hyper)")
     return parser
