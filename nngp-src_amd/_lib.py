@@ -57,6 +57,10 @@ LOO_NLPD, LOO_MSE = 0, 1
 # include/nngp_ard.h: per-feature input relevances on the nngp_mll handle; GPU library only (no host build)
 ARD_ABI_SYMBOLS = ("nngp_mll_reserve_ard", "nngp_mll_evaluate_ard", "nngp_mll_loo_evaluate_ard", "nngp_mll_ard_terms")
 
+# include/nngp_additive.h: additive kernels over feature groups; GPU library only (no host build)
+ADDITIVE_ABI_SYMBOLS = ("nngp_kernel_build_additive", "nngp_kernel_diag_additive", "nngp_model_create_additive")
+MAX_GROUPS = 1024
+
 
 class NngpArch(ctypes.Structure):
     _fields_ = [("n_dense", ctypes.c_int32), ("reserved", ctypes.c_int32),
@@ -66,6 +70,12 @@ class NngpArch(ctypes.Structure):
 class NngpArchAct(ctypes.Structure):
     _fields_ = [("base", NngpArch), ("act", ctypes.c_int32 * (MAX_DENSE - 1)),
                 ("p", (ctypes.c_double * 3) * (MAX_DENSE - 1))]
+
+
+class NngpGroups(ctypes.Structure):
+    _fields_ = [("n_groups", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("begin", ctypes.POINTER(ctypes.c_int32)), ("end", ctypes.POINTER(ctypes.c_int32)),
+                ("weight", ctypes.POINTER(ctypes.c_double)), ("full_weight", ctypes.c_double)]
 
 
 class NngpFitInfo(ctypes.Structure):
@@ -106,6 +116,7 @@ def load(knobs: bool = False):
     bind_mll_prototypes(lib)
     bind_loo_prototypes(lib)
     bind_ard_prototypes(lib)
+    bind_additive_prototypes(lib)
     _libs[knobs] = lib
     return lib
 
@@ -259,6 +270,18 @@ def bind_ard_prototypes(lib):
     return lib
 
 
+def bind_additive_prototypes(lib):
+    """Argument and result types of include/nngp_additive.h (the HIP library only)."""
+    vp, i64, i32, dbl = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_double
+    archp, groupsp = ctypes.POINTER(NngpArchAct), ctypes.POINTER(NngpGroups)
+    lib.nngp_kernel_build_additive.argtypes = [vp, i64, vp, i64, i32, archp, groupsp, i32, vp, vp, i64, i64, i64, vp]
+    lib.nngp_kernel_diag_additive.argtypes = [vp, i64, i32, archp, groupsp, vp, vp, vp]
+    lib.nngp_model_create_additive.argtypes = [ctypes.POINTER(vp), i64, i64, i32, i32, archp, groupsp, i32, dbl, i32]
+    for name in ADDITIVE_ABI_SYMBOLS:
+        getattr(lib, name).restype = ctypes.c_int
+    return lib
+
+
 def check(rc: int, lib=None):
     if rc != 0:
         msg = (lib or load()).nngp_last_error()
@@ -311,6 +334,61 @@ def make_arch_act(w_std, b_std, activations) -> NngpArchAct:
         for e, v in enumerate(spec[1:]):
             arch.p[l][e] = v
     return arch
+
+
+def pair_groups(d: int):
+    """The slot pairs of an encoded query: [(0, 2), (2, 4), ..., (d - 2, d)] -- one group per column's (upper, lower)."""
+    d = int(d)
+    if d < 2 or d % 2 != 0:
+        raise ValueError("pair groups need an even number of features >= 2, got d = %d" % d)
+    return tuple((i, i + 2) for i in range(0, d, 2))
+
+
+def check_groups(groups, weights=None, full_weight=1.0, d=None):
+    """(groups, weights, full_weight) in canonical form -- tuples of (begin, end) ints and of floats, and a float -- after the
+    checks of include/nngp_additive.h: 0 <= begin < end (<= d when d is given), finite weights >= 0, not all of them zero,
+    at most MAX_GROUPS groups.  groups = "pairs" needs d.  weights = None: every group has weight 1."""
+    if isinstance(groups, str):
+        if groups != "pairs":
+            raise ValueError("groups must be a list of (begin, end) ranges or 'pairs', got %r" % (groups,))
+        if d is None:
+            raise ValueError("groups='pairs' needs the number of features")
+        groups = pair_groups(d)
+    try:
+        out = tuple((int(b), int(e)) for b, e in groups)
+        if any(float(b) != ib or float(e) != ie for (b, e), (ib, ie) in zip(groups, out)):
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError("groups must be a list of (begin, end) integer ranges, got %r" % (groups,)) from None
+    if len(out) > MAX_GROUPS:
+        raise ValueError("at most %d groups, got %d" % (MAX_GROUPS, len(out)))
+    for b, e in out:
+        if not (0 <= b < e) or (d is not None and e > int(d)):
+            raise ValueError("group range [%d, %d) is outside 0 <= begin < end%s" % (b, e, "" if d is None else " <= d = %d" % int(d)))
+    w = (1.0,) * len(out) if weights is None else tuple(float(v) for v in weights)
+    if len(w) != len(out):
+        raise ValueError("%d groups need %d weights, got %d" % (len(out), len(out), len(w)))
+    w0 = float(full_weight)
+    if not all(np.isfinite(v) and v >= 0.0 for v in w + (w0,)):
+        raise ValueError("group weights and full_weight must be finite and >= 0")
+    if w0 == 0.0 and not any(v > 0.0 for v in w):
+        raise ValueError("all weights are zero: the additive kernel has no term")
+    return out, w, w0
+
+
+def make_groups(groups, weights, full_weight) -> NngpGroups:
+    """nngp_groups of a checked table (check_groups).  The ctypes arrays stay referenced by the result."""
+    g = NngpGroups()
+    n = len(groups)
+    g.n_groups = n
+    g._begin = (ctypes.c_int32 * max(n, 1))(*[b for b, _ in groups])
+    g._end = (ctypes.c_int32 * max(n, 1))(*[e for _, e in groups])
+    g._weight = (ctypes.c_double * max(n, 1))(*weights)
+    g.begin = ctypes.cast(g._begin, ctypes.POINTER(ctypes.c_int32))
+    g.end = ctypes.cast(g._end, ctypes.POINTER(ctypes.c_int32))
+    g.weight = ctypes.cast(g._weight, ctypes.POINTER(ctypes.c_double))
+    g.full_weight = float(full_weight)
+    return g
 
 
 def require_gpu():

@@ -31,5 +31,8 @@ def batch(kernel_fn, batch_size: int = 0, device_count: int = -1, store_on_devic
     for attr in ("w_std", "b_std", "n_relu", "activations", "all_relu"):
         setattr(batched_kernel_fn, attr, getattr(kernel_fn, attr))
     batched_kernel_fn.input_scale = getattr(kernel_fn, "input_scale", None)
+    batched_kernel_fn.groups = getattr(kernel_fn, "groups", None)
+    batched_kernel_fn.group_weights = getattr(kernel_fn, "group_weights", None)
+    batched_kernel_fn.full_weight = getattr(kernel_fn, "full_weight", 1.0)
     batched_kernel_fn.inner = kernel_fn
     return batched_kernel_fn

@@ -21,6 +21,7 @@ int make_arch_dev(const nngp_arch* arch, ArchDev* out) {
     NNGP_REQUIRE(arch->n_dense >= 1 && arch->n_dense <= NNGP_MAX_DENSE, "arch.n_dense must be in [1, %d] (got %d)",
                  NNGP_MAX_DENSE, arch->n_dense);
     out->n_dense = arch->n_dense;
+    out->groups = nullptr;
     for (int l = 0; l < NNGP_MAX_DENSE; ++l) {
         out->w2[l] = l < arch->n_dense ? arch->w_std[l] * arch->w_std[l] : 0.0;
         out->b2[l] = l < arch->n_dense ? arch->b_std[l] * arch->b_std[l] : 0.0;
@@ -127,7 +128,7 @@ static int kernel_diag(const double* x, int64_t n, int32_t d, const ArchDev& ad,
     double* q = nullptr;
     NNGP_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&q), sizeof(double) * n, s));
     int rc = launch_row_sqnorm(x, n, d, q, s);
-    if (rc == 0) rc = launch_diag_from_q(q, n, ad, diag_nngp, diag_ntk, s);
+    if (rc == 0) rc = launch_kernel_diag(x, q, n, d, ad, diag_nngp, diag_ntk, s);
     (void)hipFreeAsync(q, s);
     return rc;
 }
@@ -208,7 +209,59 @@ int nngp_kernel_build_act(const double* x1, int64_t n1, const double* x2, int64_
 }
 
 static int model_create(nngp_model** out, int64_t n_cap, int64_t m_cap, int32_t d, int32_t ny, const ArchDev* arch,
-                        int32_t get, double diag_reg, int32_t diag_reg_absolute_scale);
+                        int32_t get, double diag_reg, int32_t diag_reg_absolute_scale, const nngp_groups* groups = nullptr);
+
+// ---- include/nngp_additive.h: the stand-alone calls make their own copy of the group table and wait for their work ----
+int nngp_kernel_build_additive(const double* x1, int64_t n1, const double* x2, int64_t n2, int32_t d, const nngp_arch_act* arch,
+                               const nngp_groups* groups, int32_t out_dtype, void* out_nngp, void* out_ntk, int64_t ld,
+                               int64_t row_begin, int64_t row_end, void* stream) {
+    ArchDev ad{};
+    NNGP_TRY(make_arch_dev_act(arch, &ad));
+    NNGP_REQUIRE(d > 0, "kernel_build: bad n1/n2/d");
+    GroupsDev gd{};
+    bool plain = false;
+    NNGP_TRY(groups_create(groups, d, &gd, &plain));
+    if (!plain) ad.groups = &gd;
+    int rc = kernel_build(x1, n1, x2, n2, d, ad, out_dtype, out_nngp, out_ntk, ld, row_begin, row_end, stream);
+    if (!plain) {
+        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == 0) {
+            set_error("kernel_build_additive: the stream reported an error");
+            rc = -1;
+        }
+        groups_destroy(&gd);
+    }
+    return rc;
+}
+
+int nngp_kernel_diag_additive(const double* x, int64_t n, int32_t d, const nngp_arch_act* arch, const nngp_groups* groups,
+                              double* diag_nngp, double* diag_ntk, void* stream) {
+    ArchDev ad{};
+    NNGP_TRY(make_arch_dev_act(arch, &ad));
+    NNGP_REQUIRE(d > 0, "kernel_diag: bad arguments");
+    GroupsDev gd{};
+    bool plain = false;
+    NNGP_TRY(groups_create(groups, d, &gd, &plain));
+    if (!plain) ad.groups = &gd;
+    int rc = kernel_diag(x, n, d, ad, diag_nngp, diag_ntk, stream);
+    if (!plain) {
+        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == 0) {
+            set_error("kernel_diag_additive: the stream reported an error");
+            rc = -1;
+        }
+        groups_destroy(&gd);
+    }
+    return rc;
+}
+
+int nngp_model_create_additive(nngp_model** out, int64_t n_cap, int64_t m_cap, int32_t d, int32_t ny, const nngp_arch_act* arch,
+                               const nngp_groups* groups, int32_t get, double diag_reg, int32_t diag_reg_absolute_scale) {
+    NNGP_REQUIRE(out != nullptr, "model_create: out is NULL");
+    *out = nullptr;
+    ArchDev ad{};
+    NNGP_TRY(make_arch_dev_act(arch, &ad));
+    NNGP_REQUIRE(groups != nullptr, "groups: the group table is NULL");
+    return model_create(out, n_cap, m_cap, d, ny, &ad, get, diag_reg, diag_reg_absolute_scale, groups);
+}
 
 int nngp_model_create(nngp_model** out, int64_t n_cap, int64_t m_cap, int32_t d, int32_t ny, const nngp_arch* arch,
                       int32_t get, double diag_reg, int32_t diag_reg_absolute_scale) {
@@ -229,7 +282,7 @@ int nngp_model_create_act(nngp_model** out, int64_t n_cap, int64_t m_cap, int32_
 }
 
 static int model_create(nngp_model** out, int64_t n_cap, int64_t m_cap, int32_t d, int32_t ny, const ArchDev* arch,
-                        int32_t get, double diag_reg, int32_t diag_reg_absolute_scale) {
+                        int32_t get, double diag_reg, int32_t diag_reg_absolute_scale, const nngp_groups* groups) {
     NNGP_REQUIRE(n_cap > 0 && d > 0 && ny > 0 && m_cap >= 0, "model_create: bad sizes");
     NNGP_REQUIRE(get == NNGP_GET_NNGP || get == NNGP_GET_NTK, "model_create: get must be NNGP_GET_NNGP or NNGP_GET_NTK");
     NNGP_REQUIRE(diag_reg >= 0.0, "model_create: diag_reg must be >= 0");
@@ -237,6 +290,15 @@ static int model_create(nngp_model** out, int64_t n_cap, int64_t m_cap, int32_t 
     NNGP_REQUIRE(m != nullptr, "model_create: out of host memory");
     int rc = 0;
     m->arch = *arch;
+    if (groups != nullptr) {  // the model's own copy of the group table (include/nngp_additive.h)
+        bool plain = false;
+        rc = groups_create(groups, d, &m->groups, &plain);
+        if (rc != 0) {
+            delete m;
+            return rc;
+        }
+        if (!plain) m->arch.groups = &m->groups;
+    }
     m->n_cap = n_cap; m->np_cap = round_up(n_cap, TB); m->m_cap = 0;
     m->ld = m->np_cap;
     m->d = d; m->ny = ny; m->get = get; m->diag_reg = diag_reg; m->absolute = diag_reg_absolute_scale;
@@ -346,7 +408,7 @@ int nngp_model_set_train(nngp_model* m, const double* x, const double* y, int64_
     NNGP_HIP_CHECK(hipMemcpyAsync(m->x, x, sizeof(double) * n * m->d, hipMemcpyDeviceToDevice, s));
     NNGP_HIP_CHECK(hipMemcpyAsync(m->y, y, sizeof(double) * n * m->ny, hipMemcpyDeviceToDevice, s));
     NNGP_TRY(launch_row_sqnorm(m->x, n, m->d, m->q, s));
-    NNGP_TRY(launch_diag_from_q(m->q, n, m->arch, m->get == NNGP_GET_NNGP ? m->kdiag : nullptr,
+    NNGP_TRY(launch_kernel_diag(m->x, m->q, n, m->d, m->arch, m->get == NNGP_GET_NNGP ? m->kdiag : nullptr,
                                 m->get == NNGP_GET_NTK ? m->kdiag : nullptr, s));
     hipLaunchKernelGGL(k_sum, dim3(1), dim3(1024), 0, s, m->kdiag, n, m->pcg.scal + 6);  // [6] = max, [7] = sum
     NNGP_HIP_CHECK(hipMemcpyAsync(m->pcg.host_scal + 6, m->pcg.scal + 6, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -567,7 +629,7 @@ int nngp_model_append(nngp_model* m, const double* x_new, const double* y_new, i
     NNGP_HIP_CHECK(hipMemcpyAsync(m->x + n0 * m->d, x_new, sizeof(double) * b * m->d, hipMemcpyDeviceToDevice, s));
     NNGP_HIP_CHECK(hipMemcpyAsync(m->y + n0 * m->ny, y_new, sizeof(double) * b * m->ny, hipMemcpyDeviceToDevice, s));
     NNGP_TRY(launch_row_sqnorm(m->x + n0 * m->d, b, m->d, m->q + n0, s));
-    NNGP_TRY(launch_diag_from_q(m->q + n0, b, m->arch, m->get == NNGP_GET_NNGP ? m->kdiag + n0 : nullptr,
+    NNGP_TRY(launch_kernel_diag(m->x + n0 * m->d, m->q + n0, b, m->d, m->arch, m->get == NNGP_GET_NNGP ? m->kdiag + n0 : nullptr,
                                 m->get == NNGP_GET_NTK ? m->kdiag + n0 : nullptr, s));
     hipLaunchKernelGGL(k_sum, dim3(1), dim3(1024), 0, s, m->kdiag, n1, m->pcg.scal + 6);
     NNGP_HIP_CHECK(hipMemcpyAsync(m->pcg.host_scal + 6, m->pcg.scal + 6, 2 * sizeof(double), hipMemcpyDeviceToHost, s));

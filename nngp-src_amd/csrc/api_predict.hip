@@ -735,7 +735,7 @@ static int predict_impl(nngp_model* m, const double* x_test, int64_t mt, int32_t
     const double kFlagThr = (NNGP_KNOB(6) >= 2 && NNGP_KNOB(6) <= 30) ? pow(10.0, -(double)NNGP_KNOB(6)) : 1e-8;
     auto cov_part = [&]() -> int {
     if (full) NNGP_TRY(ensure_full_cov_capacity(m, mt));
-    NNGP_TRY(launch_diag_from_q(qt, mt, m->arch, m->tt_diag, nullptr, s));  // NNGP K(x_t, x_t)
+    NNGP_TRY(launch_kernel_diag(xt, qt, mt, m->d, m->arch, m->tt_diag, nullptr, s));  // NNGP K(x_t, x_t)
     auto build_ktt = [&]() -> int {  // NNGP K_tt [mt, mt] into ktt64 (ld = mp)
         BuildArgs a{};
         a.x1 = xt; a.x2 = xt; a.q1 = qt; a.q2 = qt;

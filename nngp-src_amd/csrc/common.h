@@ -10,6 +10,7 @@
 #include "../../include/nngp_rbf_gp.h"
 #include "../../include/nngp_activations.h"
 #include "../../include/nngp_mll.h"
+#include "../../include/nngp_additive.h"
 
 namespace nngp {
 
@@ -87,6 +88,16 @@ static inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * 
 // of the ReLU instantiations, ArchRelu in kernel_build.hip, has exactly this layout); the rest says which hidden layer applies
 // which activation (include/nngp_activations.h), with the parameters of its closed form precomputed:
 //   ABRelu(a, b): ap = {a b, (b - a)^2, (a^2 + b^2) / 2, 0};   Erf(a, b, c): ap = {2 a^2 / pi, 2 b^2, c^2, 4 a^2 b^2 / pi}
+// The group table of an additive kernel (include/nngp_additive.h) on the device: the groups with a non-zero weight, in the
+// caller's order.  One allocation (weight), owned by whoever made it (groups_create / groups_destroy).
+struct GroupsDev {
+    int n_groups;
+    double full_weight;
+    const double* weight;  // device [n_groups]
+    const int* begin;      // device [n_groups]
+    const int* end;        // device [n_groups]
+};
+
 struct ArchDev {
     int n_dense;
     double w2[NNGP_MAX_DENSE];
@@ -94,6 +105,7 @@ struct ArchDev {
     int general;                            // 0: every hidden layer is ReLU (act / ap unused)
     int act[NNGP_MAX_DENSE - 1];            // NNGP_ACT_* of hidden layer l (after Dense layer l)
     double ap[NNGP_MAX_DENSE - 1][4];
+    const GroupsDev* groups;                // host pointer; NULL: the kernel of the whole input alone
 };
 
 int make_arch_dev(const nngp_arch* arch, ArchDev* out);
@@ -122,7 +134,19 @@ struct BuildArgs {
 };
 int launch_row_sqnorm(const double* x, int64_t n, int d, double* q, hipStream_t s);
 int launch_diag_from_q(const double* q, int64_t n, const ArchDev& arch, double* dn, double* dt, hipStream_t s);
-int launch_kernel_build(const BuildArgs& a, const ArchDev& arch, hipStream_t s);
+int launch_kernel_build(const BuildArgs& a, const ArchDev& arch, hipStream_t s);  // arch.groups: the summed kernel
+int launch_kernel_build_plain(const BuildArgs& a, const ArchDev& arch, hipStream_t s);  // the whole-input term alone
+// K's diagonal of rows x (q = |x|^2 / d): launch_diag_from_q, or the grouped diagonal when arch.groups is set
+int launch_kernel_diag(const double* x, const double* q, int64_t n, int d, const ArchDev& arch, double* dn, double* dt,
+                       hipStream_t s);
+
+// ---- kernel_build_additive.hip ----
+// *plain: n_groups = 0 and full_weight = 1 -- nothing to add (out is left empty, and ArchDev::groups stays NULL)
+int groups_create(const nngp_groups* g, int d, GroupsDev* out, bool* plain);
+void groups_destroy(GroupsDev* g);
+int launch_kernel_build_additive(const BuildArgs& a, const ArchDev& arch, hipStream_t s);
+int launch_diag_additive(const double* x, const double* q, int64_t n, int d, const ArchDev& arch, double* dn, double* dt,
+                         hipStream_t s);
 
 // ---- gemm_f32.hip ----
 // tri: the square B is lower (1) / upper (2) triangular -- every column tile only walks the k range where its rows of B are non-zero

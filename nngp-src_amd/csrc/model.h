@@ -49,6 +49,7 @@ struct nngp_model {
     int64_t n_cap = 0, np_cap = 0, m_cap = 0;
     int d = 0, ny = 1, get = NNGP_GET_NNGP;
     ArchDev arch{};
+    GroupsDev groups{};  // additive kernel: the table arch.groups points to (empty otherwise)
     double diag_reg = 1e-3;
     int absolute = 0;
 
@@ -183,6 +184,7 @@ struct nngp_model {
     ~nngp_model() {
         dev_free(x); dev_free(y); dev_free(q); dev_free(kdiag); dev_free(k64); dev_free(a32); dev_free(dinv);
         dev_free(clamped); dev_free(alpha);
+        groups_destroy(&groups);
         dev_free(pcg.r); dev_free(pcg.z); dev_free(pcg.p); dev_free(pcg.q); dev_free(pcg.xcol); dev_free(pcg.bcol);
         dev_free(pcg.f32a); dev_free(pcg.f32b); dev_free(pcg.f32c); dev_free(pcg.scal); dev_free(pcg.symv_part); dev_free(pcg.dot_part); dev_free(pcg.dot_ctr);
         if (pcg.host_scal) (void)hipHostFree(pcg.host_scal);

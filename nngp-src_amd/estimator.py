@@ -19,12 +19,13 @@ from .batching import batch
 class Estimator(object):
     def __init__(self, schema_name: str, data_path: str, train_query_path: str, chunk_size: int = 64,
                  use_aux: bool = False, q_error_threshold: float = 100.0, coef_var_threshold: float = 1.0,
-                 encoder=None, kernel_type: str = "nngp", serving: bool = True):
+                 encoder=None, kernel_type: str = "nngp", serving: bool = True, groups=None):
         self.schema_name = schema_name
         self.data_path = data_path
         self.train_query_path = train_query_path
         self.chunk_size = chunk_size
         self.kernel_type = kernel_type
+        self.groups = groups  # None, "pairs" or (begin, end) feature ranges: the additive kernel (stax.additive), all weights 1
         self.serving = serving  # load_model also builds the explicit float64 inverse: predict = one product per batch
         print("loading schema and training data ... This may take seconds ...")
         if encoder is None:
@@ -43,6 +44,8 @@ class Estimator(object):
             self._native = None
         print("Building model kernel ...")
         init_fn, apply_fn, kernel_fn = stax.serial(stax.Dense(512), stax.Relu(), stax.Dense(1))
+        if groups is not None:
+            kernel_fn = kernel_fn.with_groups(groups)
         kernel_fn = batch(kernel_fn, device_count=0, batch_size=0)
         self.predict_fn = nt_predict.gradient_descent_mse_ensemble(kernel_fn, self.X_train, self.Y_train, diag_reg=1e-3)
 

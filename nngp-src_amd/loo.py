@@ -22,7 +22,7 @@ import numpy as np
 from . import _lib
 from .gp import F64Handle, train_hyperparameters
 from .mll import (_Params, _arch_of, _ard_terms, _relevance_arg, _reserve_ard, _train_arrays, rebuild_kernel_fn,
-                  evaluate_once, finish_kernel_fn, relevance_groups, relevance_of, split_input_scale, tune_loop)
+                  evaluate_once, finish_kernel_fn, reject_groups, relevance_groups, relevance_of, split_input_scale, tune_loop)
 
 OBJECTIVES = {"nlpd": _lib.LOO_NLPD, "mse": _lib.LOO_MSE}
 _GET = {"nngp": _lib.GET_NNGP, "ntk": _lib.GET_NTK}
@@ -39,6 +39,7 @@ def check_supported(kernel_fn_or_params, get="nngp", objective="mse", with_grad=
         raise ValueError("the NTK mean is kernel ridge regression with Theta: it has no leave-one-out variance, so no nlpd")
     if get == "ntk" and with_grad:
         raise ValueError("no leave-one-out gradient for the NTK (its ensemble posterior is not a GP with prior Theta)")
+    reject_groups(kernel_fn_or_params, "leave-one-out")
     w, b, acts = _arch_of(kernel_fn_or_params)
     for l, a in enumerate(acts):
         if a[0] == "erf":

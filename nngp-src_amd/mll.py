@@ -37,11 +37,20 @@ def _arch_of(kernel_fn_or_params):
     return w, b, acts
 
 
+def reject_groups(kernel_fn_or_params, what):
+    """ValueError for a kernel_fn that carries feature groups (stax.additive): the evidence and leave-one-out passes build the
+    plain kernel, and the gradient with respect to the group weights does not exist yet."""
+    if getattr(kernel_fn_or_params, "groups", None) is not None:
+        raise ValueError("%s does not cover the additive kernel over feature groups (kernel_fn.groups is set): evaluate or "
+                         "tune the plain kernel_fn, then add the groups with kernel_fn.with_groups(...)" % what)
+
+
 def check_supported(kernel_fn_or_params, get="nngp"):
     """ValueError (no GPU call) for what the marginal likelihood does not cover: the NTK and Erf layers."""
     if get != "nngp":
         raise ValueError("the marginal likelihood is that of the NNGP posterior (get='nngp'); the NTK ensemble posterior "
                          "is not a GP with prior Theta, got get=%r" % (get,))
+    reject_groups(kernel_fn_or_params, "the marginal likelihood")
     w, b, acts = _arch_of(kernel_fn_or_params)
     for l, a in enumerate(acts):
         if a[0] == "erf":

@@ -18,14 +18,32 @@ _COV = {False: _lib.COV_NONE, None: _lib.COV_NONE, "none": _lib.COV_NONE, "diag"
         True: _lib.COV_FULL, "full": _lib.COV_FULL}
 
 
+def groups_to_fields(groups, group_weights, full_weight) -> dict:
+    """The optional checkpoint fields of a group table (none without groups)."""
+    if groups is None:
+        return {}
+    return {"groups": np.array(groups, dtype=np.int64).reshape(-1, 2), "group_weights": np.array(group_weights, dtype=np.float64),
+            "full_weight": np.array(float(full_weight))}
+
+
+def groups_from_fields(z) -> dict:
+    """GPModel's group arguments from a loaded checkpoint (empty when it has no group table)."""
+    if "groups" not in z.files:
+        return {}
+    return dict(groups=[(int(b), int(e)) for b, e in z["groups"]], group_weights=[float(v) for v in z["group_weights"]],
+                full_weight=float(z["full_weight"]))
+
+
 class GPModel:
     def __init__(self, n_cap: int, d: int, w_std, b_std, get: str = "nngp", diag_reg: float = 1e-3,
                  diag_reg_absolute_scale: bool = False, ny: int = 1, m_cap: int = 0, knobs: bool = False,
-                 activations=None, input_scale=None):
+                 activations=None, input_scale=None, groups=None, group_weights=None, full_weight=1.0):
         """activations: one per hidden layer, as ``stax.KernelFn.activations`` (None: all ReLU).  An all-ReLU model is
         created through nngp_model_create, any other through nngp_model_create_act.  input_scale: None, or d values >= 0 that
         multiply the features of every X that enters (fit, set_train, append, predict, pool scoring) on the device, as
-        ``stax.KernelFn.input_scale`` does for the kernel."""
+        ``stax.KernelFn.input_scale`` does for the kernel.  groups: None, "pairs" or (begin, end) feature ranges -- the additive
+        kernel full_weight K(x, x') + sum_g group_weights[g] K(x_g, x'_g) of include/nngp_additive.h (group_weights = None: all 1),
+        created through nngp_model_create_additive; the input scale is applied first."""
         from .stax import check_input_scale
         self.input_scale = check_input_scale(input_scale)
         if self.input_scale is not None and self.input_scale.shape[0] != int(d):
@@ -40,7 +58,15 @@ class GPModel:
         self.activations = tuple(_lib.canonical_activation(a) for a in (activations or [("relu",)] * n_hidden))
         self.all_relu = _lib.all_relu(self.activations)
         self.handle = ctypes.c_void_p()
-        if self.all_relu:
+        self.groups, self.group_weights, self.full_weight = None, None, 1.0
+        if groups is not None:
+            self.groups, self.group_weights, self.full_weight = _lib.check_groups(groups, group_weights, full_weight, d=int(d))
+            arch_act = _lib.make_arch_act(w_std, b_std, self.activations)
+            table = _lib.make_groups(self.groups, self.group_weights, self.full_weight)
+            self._check(self.lib.nngp_model_create_additive(ctypes.byref(self.handle), int(n_cap), int(m_cap), int(d), int(ny),
+                                                           ctypes.byref(arch_act), ctypes.byref(table), _GET[get],
+                                                           float(diag_reg), int(bool(diag_reg_absolute_scale))))
+        elif self.all_relu:
             self._check(self.lib.nngp_model_create(ctypes.byref(self.handle), int(n_cap), int(m_cap), int(d), int(ny),
                                                   ctypes.byref(self.arch), _GET[get], float(diag_reg),
                                                   int(bool(diag_reg_absolute_scale))))
@@ -229,6 +255,7 @@ class GPModel:
         extra = {}
         if self.input_scale is not None:  # optional field of either version; a file without it loads as before
             extra["input_scale"] = np.array(self.input_scale)
+        extra.update(groups_to_fields(self.groups, self.group_weights, self.full_weight))  # optional; a file without them loads as before
         if not self.all_relu:  # v2: the activations as (code, a, b, c) rows; a ReLU model keeps writing v1
             codes = {"relu": _lib.ACT_RELU, "abrelu": _lib.ACT_ABRELU, "erf": _lib.ACT_ERF}
             extra["activations"] = np.array([[codes[a[0]]] + list(a[1:]) + [0.0] * (4 - len(a)) for a in self.activations],
@@ -257,9 +284,10 @@ class GPModel:
                 kind = names[int(row[0])]
                 acts.append((kind,) + tuple(float(v) for v in row[1:1 + nparams[kind]]))
         x, y = z["x"], z["y"]
+        grouped = groups_from_fields(z)
         model = cls(max(int(z["n_cap"]), x.shape[0]), x.shape[1], z["w_std"].tolist(), z["b_std"].tolist(), get=str(z["get"]),
                     diag_reg=float(z["diag_reg"]), diag_reg_absolute_scale=bool(z["absolute"]), ny=y.shape[1], m_cap=m_cap,
-                    activations=acts, input_scale=(z["input_scale"] if "input_scale" in z.files else None))
+                    activations=acts, input_scale=(z["input_scale"] if "input_scale" in z.files else None), **grouped)
         model.fit(x, y)
         if check:
             a, a0 = model.alpha().cpu().numpy(), z["alpha"]

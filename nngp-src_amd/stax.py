@@ -93,10 +93,21 @@ def apply_input_scale(scale, xd):
 class KernelFn:
     """kernel_fn(x1, x2=None, get=None): closed-form kernel of Dense,(act,Dense)* on the GPU."""
 
-    def __init__(self, w_std, b_std, activations=None, input_scale=None):
+    def __init__(self, w_std, b_std, activations=None, input_scale=None, groups=None, group_weights=None, full_weight=1.0):
         """input_scale: None or d values >= 0 that multiply the features of x1 and x2 on the device before the build --
-        sqrt of the relevances of include/nngp_ard.h (with_input_scale returns a copy that carries them)."""
+        sqrt of the relevances of include/nngp_ard.h (with_input_scale returns a copy that carries them).
+        groups: None, "pairs" or (begin, end) feature ranges -- the additive kernel of include/nngp_additive.h,
+        full_weight K(x, x') + sum_g group_weights[g] K(x_g, x'_g) (with_groups returns a copy that carries them)."""
         self.input_scale = check_input_scale(input_scale)
+        if groups is None:
+            self.groups, self.group_weights, self.full_weight = None, None, 1.0
+        elif isinstance(groups, str):
+            _lib.check_groups(groups, None, full_weight, d=2)  # the name and full_weight; the table is made per call, from d
+            self.groups, self.group_weights, self.full_weight = groups, None, float(full_weight)
+            if group_weights is not None:
+                raise ValueError("groups='pairs' takes no weights: give the ranges (stax.pair_groups(d)) to weight them")
+        else:
+            self.groups, self.group_weights, self.full_weight = _lib.check_groups(groups, group_weights, full_weight)
         self.w_std = tuple(float(w) for w in w_std)
         self.b_std = tuple(float(b) for b in b_std)
         self.n_relu = len(self.w_std) - 1  # hidden layers (the name is the all-ReLU one)
@@ -109,7 +120,17 @@ class KernelFn:
 
     def with_input_scale(self, scale):
         """A copy of this kernel_fn with ``input_scale = scale`` (None: without one)."""
-        return KernelFn(self.w_std, self.b_std, self.activations, scale)
+        return KernelFn(self.w_std, self.b_std, self.activations, scale, self.groups, self.group_weights, self.full_weight)
+
+    def with_groups(self, groups, weights=None, full_weight=1.0):
+        """A copy of this kernel_fn with the additive kernel over ``groups`` (None: the plain kernel again)."""
+        return KernelFn(self.w_std, self.b_std, self.activations, self.input_scale, groups, weights, full_weight)
+
+    def group_table(self, d):
+        """None, or (groups, weights, full_weight) checked against d features."""
+        if self.groups is None:
+            return None
+        return _lib.check_groups(self.groups, self.group_weights, self.full_weight, d=d)
 
     def _arch(self):
         if self.all_relu:
@@ -137,11 +158,19 @@ class KernelFn:
         r0, r1 = (0, n1) if rows is None else (int(rows[0]), int(rows[1]))
         outs = {g: torch.empty((n1, n2), dtype=torch.float64, device=dev) for g in set(gets)}
         if n1 > 0 and n2 > 0 and r1 > r0:
-            arch = self._arch()
-            build = lib.nngp_kernel_build if self.all_relu else lib.nngp_kernel_build_act
-            _lib.check(build(_lib.ptr(x1d), n1, _lib.ptr(x2d), n2, d, ctypes.byref(arch),
-                                             _lib.DTYPE_F64, _lib.ptr(outs.get("nngp")), _lib.ptr(outs.get("ntk")),
-                                             n2, r0, r1, _lib.stream_ptr()))
+            table = self.group_table(d)
+            if table is not None:
+                arch = _lib.make_arch_act(self.w_std, self.b_std, self.activations)
+                gr = _lib.make_groups(*table)
+                _lib.check(lib.nngp_kernel_build_additive(_lib.ptr(x1d), n1, _lib.ptr(x2d), n2, d, ctypes.byref(arch),
+                                                          ctypes.byref(gr), _lib.DTYPE_F64, _lib.ptr(outs.get("nngp")),
+                                                          _lib.ptr(outs.get("ntk")), n2, r0, r1, _lib.stream_ptr()))
+            else:
+                arch = self._arch()
+                build = lib.nngp_kernel_build if self.all_relu else lib.nngp_kernel_build_act
+                _lib.check(build(_lib.ptr(x1d), n1, _lib.ptr(x2d), n2, d, ctypes.byref(arch),
+                                                 _lib.DTYPE_F64, _lib.ptr(outs.get("nngp")), _lib.ptr(outs.get("ntk")),
+                                                 n2, r0, r1, _lib.stream_ptr()))
         res = {g: (t[r0:r1] if rows is not None else t) for g, t in outs.items()}
         if as_numpy:
             res = {g: t.cpu().numpy() for g, t in res.items()}
@@ -150,6 +179,18 @@ class KernelFn:
         if isinstance(get, str):
             return res[get]
         return collections.namedtuple("Kernel", gets)(*[res[g] for g in gets])
+
+
+pair_groups = _lib.pair_groups
+
+
+def additive(layers, groups, weights=None, full_weight=1.0):
+    """serial(*layers) with the additive kernel over feature groups: (init_fn, apply_fn, kernel_fn), where
+    kernel_fn(x, x') = full_weight K(x, x') + sum_g weights[g] K(x[:, b_g:e_g], x'[:, b_g:e_g]) and K is serial(*layers)'s
+    kernel (include/nngp_additive.h).  groups: (begin, end) ranges, or "pairs".  init_fn / apply_fn are those of one
+    network of the sum."""
+    init_fn, apply_fn, kernel_fn = serial(*layers)
+    return init_fn, apply_fn, kernel_fn.with_groups(groups, weights, full_weight)
 
 
 def serial(*layers):

@@ -57,6 +57,8 @@ def NNGP_train_and_test(args, X_train, Y_train, X_test, Y_test, query_infos_trai
 
     if kernel_fn is None:
         init_fn, apply_fn, kernel_fn = kernel_fn_from_args(args)
+    if getattr(args, "additive", "none") == "pairs":  # slot pairs + the whole input (tuning, above, is the plain kernel's)
+        kernel_fn = kernel_fn.with_groups("pairs", full_weight=getattr(args, "additive_full_weight", 1.0))
     kernel_fn = batch(kernel_fn, device_count=0, batch_size=0)
     start = datetime.datetime.now()
     predict_fn = nt_predict.gradient_descent_mse_ensemble(kernel_fn, X_train, Y_train, diag_reg=diag_reg)
@@ -196,6 +198,11 @@ def make_parser():
                         help="with --tune_hyper: also tune one relevance per input feature (W_std of the first layer is then fixed)")
     parser.add_argument("--ard_groups", type=str, default="none", choices=("none", "pairs"),
                         help="--tune_ard: 'pairs' ties features 2i and 2i+1, the two ends of a column's range")
+    parser.add_argument("--additive", type=str, default="none", choices=("none", "pairs"),
+                        help="'pairs': the additive kernel -- one network per column's (upper, lower) slot pair plus the whole input "
+                             "(--tune_hyper and --loo work on the plain kernel only)")
+    parser.add_argument("--additive_full_weight", type=float, default=1.0,
+                        help="--additive: weight of the whole-input term (0 leaves it out)")
     parser.add_argument("--tune_lr", type=float, default=0.05, help="step size of --tune_hyper")
     parser.add_argument("--b_std_init", type=float, default=None, help="start of b_std for layers with b_std = 0 (--tune_hyper)")
     return parser
