@@ -61,6 +61,9 @@ ARD_ABI_SYMBOLS = ("nngp_mll_reserve_ard", "nngp_mll_evaluate_ard", "nngp_mll_lo
 ADDITIVE_ABI_SYMBOLS = ("nngp_kernel_build_additive", "nngp_kernel_diag_additive", "nngp_model_create_additive")
 MAX_GROUPS = 1024
 
+# include/nngp_pool.h: batch-aware pool selection (greedy by conditional variance); GPU library only (no host build)
+POOL_ABI_SYMBOLS = ("nngp_pool_select_greedy",)
+
 
 class NngpArch(ctypes.Structure):
     _fields_ = [("n_dense", ctypes.c_int32), ("reserved", ctypes.c_int32),
@@ -117,6 +120,7 @@ def load(knobs: bool = False):
     bind_loo_prototypes(lib)
     bind_ard_prototypes(lib)
     bind_additive_prototypes(lib)
+    bind_pool_prototypes(lib)
     _libs[knobs] = lib
     return lib
 
@@ -278,6 +282,15 @@ def bind_additive_prototypes(lib):
     lib.nngp_kernel_diag_additive.argtypes = [vp, i64, i32, archp, groupsp, vp, vp, vp]
     lib.nngp_model_create_additive.argtypes = [ctypes.POINTER(vp), i64, i64, i32, i32, archp, groupsp, i32, dbl, i32]
     for name in ADDITIVE_ABI_SYMBOLS:
+        getattr(lib, name).restype = ctypes.c_int
+    return lib
+
+
+def bind_pool_prototypes(lib):
+    """Argument and result types of include/nngp_pool.h (the HIP library only)."""
+    vp, i64, dbl = ctypes.c_void_p, ctypes.c_int64, ctypes.c_double
+    lib.nngp_pool_select_greedy.argtypes = [vp, i64, i64, dbl, i64, vp, vp, vp, i64, vp]
+    for name in POOL_ABI_SYMBOLS:
         getattr(lib, name).restype = ctypes.c_int
     return lib
 

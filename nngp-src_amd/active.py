@@ -12,6 +12,10 @@ uniforms -> Gumbel top-k), on the device (``nngp_pool_select``), in the host bui
 reference's draw index for index wherever jax's own ``log`` and ours round alike (pinned by the Random123 vectors of Threefry, not
 against jax itself, which is not installable here).  NaN scores (a NaN variance or mean): the reference's argsort puts NaN LAST,
 i.e. its top-k path would select them first and its biased path never; here a NaN score never wins in either path.
+
+``selection="greedy"`` (``active_train.py --greedy``) replaces both rules by a batch-aware one: greedy picks by conditional variance on
+the pool's full posterior covariance (``GPModel.select_pool(method="greedy")``, ``pool.py``), so that two near-identical pool queries
+are not both labelled.  ``None``, the default, is the reference's behaviour above.
 """
 from __future__ import annotations
 
@@ -38,13 +42,40 @@ def _same_scale(a, b):
     return (a is None and b is None) or (a is not None and b is not None and np.array_equal(a, b))
 
 
+def greedy_select(cov, count, noise=0.0):
+    """The rule of include/nngp_pool.h in NumPy, for a predict_fn without a device model: `count` indices of cov [m, m], each the one
+    with the largest variance given the picks before it (observed with `noise`); equal variances go to the lowest index, a NaN never
+    wins, and a pivot that is not positive conditions nothing."""
+    cov = np.asarray(cov, dtype=np.float64)
+    m = cov.shape[0]
+    d = np.diag(cov).copy()
+    picked = np.zeros(m, dtype=bool)  # the exclusion is a mask: it does not depend on what the residual d becomes
+    picks = np.zeros(count, dtype=np.int64)
+    factor = np.zeros((count, m))
+    for j in range(count):
+        key = np.where(np.isnan(d) | (d == -np.inf), -np.finfo(np.float64).max, d)  # NaN (and -inf) below every number ...
+        key[picked] = -np.inf                                                       # ... and a picked index below those
+        p = int(np.argmax(key))  # the first of equal maxima
+        picks[j] = p
+        pivot = d[p] + noise
+        if pivot > 0.0:
+            with np.errstate(over="ignore", invalid="ignore"):
+                factor[j] = (cov[:, p] - factor[:j].T @ factor[:j, p]) / np.sqrt(pivot)
+                d = d - factor[j] * factor[j]
+        picked[p] = True
+    return picks
+
+
 class ActiveLearner(object):
-    def __init__(self, args=None, budget=1000, active_iters=3, kernel_type="nngp", biased_sample=True):
+    def __init__(self, args=None, budget=1000, active_iters=3, kernel_type="nngp", biased_sample=True, selection=None):
         self.args = args
         self.budget = getattr(args, "budget", budget)
         self.active_iters = getattr(args, "active_iters", active_iters)
         self.kernel_type = getattr(args, "kernel_type", kernel_type)
         self.biased_sample = getattr(args, "biased_sample", biased_sample)
+        self.selection = getattr(args, "selection", selection)  # None: biased_sample decides (the reference); "greedy"
+        if self.selection not in (None, "greedy"):
+            raise ValueError("selection must be None or 'greedy', got %r" % (self.selection,))
         self.pred_stat = PredictionStatistics()
         self._model = None
         self._fitted = None      # (X, Y) of the last fit, to recognise an appended training set
@@ -104,8 +135,14 @@ class ActiveLearner(object):
         model = self._model if getattr(predict_fn, "learner", None) is self else None
         if model is not None and num_test > 0:
             assert kernel_type == model.get, "active_test: the fitted model is a %r posterior" % model.get
+            if self.selection == "greedy":  # conditional-variance picks on the pool's full covariance, on the GPU
+                return model.select_pool(X_test, num_select, method="greedy")
             # std / max(mean), top-`budget` or the std-proportional draw, all on the GPU: only the indices come back
             return model.select_pool(X_test, num_select, biased=self.biased_sample, seed=10)
+        if self.selection == "greedy":
+            # without a device model the observation noise is whatever the predict_fn states as its `noise` (else 0)
+            _, pred_cov = predict_fn(x_test=X_test, get=kernel_type, compute_cov=True)
+            return greedy_select(pred_cov, num_select, float(getattr(predict_fn, "noise", 0.0)))
         pred_mean, pred_var = predict_fn(x_test=X_test, get=kernel_type, compute_cov="diag")
         pred_std = np.sqrt(np.maximum(pred_var, 0.0))
         pred_std = pred_std / np.max(pred_mean, 0)

@@ -5,7 +5,7 @@ Same flow and prints: load the encoded queries, 20 / 60 / 20 split with seed 10 
 ``train_test_val_split(X, Y, train_frac=0.2, test_frac=0.6)``, active_train.py:26-27), ``Dense(512)-Relu-Dense(1)``, then
 ``ActiveLearner.active_train`` -- fit, score the pool by predictive std / max(mean), move ``--budget`` queries into the training set
 (default: the std-proportional draw of ``--biased_sample True``, the reference's ``jax.random.choice`` restated in ``jaxrand.py``),
-refit, ``--active_iters`` times; the GP runs on the MI355X through libnngp_hip.so and every refit after the first EXTENDS the
+refit, ``--active_iters`` times (``--greedy``: the batch-aware rule of ``pool.py`` instead, greedy picks by conditional variance); the GP runs on the MI355X through libnngp_hip.so and every refit after the first EXTENDS the
 factor (``nngp_model_append``).
 
 Data: the reference reads ``schemas.load_training_schema_data(args)`` (benchmark CSVs of yelp / tpcds / tpch / imdb, not shipped);
@@ -74,7 +74,10 @@ def make_parser():
     parser.add_argument("--data_path", type=str, default='')
     parser.add_argument("--schema_name", type=str, default='tpch', help='yelp, tpcds, tpch')
     # additions
-    parser.add_argument("--top_k", action='store_true', help="select the `budget` largest scores instead of the biased draw")
+    rule = parser.add_mutually_exclusive_group()  # one selection rule at a time
+    rule.add_argument("--top_k", action='store_true', help="select the `budget` largest scores instead of the biased draw")
+    rule.add_argument("--greedy", action='store_true',
+                      help="select the batch greedily by conditional variance (pool covariance, picks conditioned on one another)")
     parser.add_argument("--n_relu", type=int, default=1, help="hidden layers (reference: 1)")
     parser.add_argument("--activation", type=str, default="relu", choices=ACTIVATIONS, help="activation of every hidden layer")
     parser.add_argument("--leaky_alpha", type=float, default=0.1, help="negative slope of --activation leaky_relu")
@@ -86,6 +89,7 @@ def parse_args(argv=None):
     args = make_parser().parse_args(argv)
     if args.top_k:
         args.biased_sample = False
+    args.selection = "greedy" if args.greedy else None
     args.cuda = True
     args.join_query = len(args.relations.split(',')) > 1
     return args

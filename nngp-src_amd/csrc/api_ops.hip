@@ -166,6 +166,25 @@ int nngp_pool_select(const double* mean, int64_t m, int32_t ny, const double* va
     return rc;
 }
 
+int nngp_pool_select_greedy(const double* cov, int64_t m, int64_t ld, double noise, int64_t count, int64_t* indices, double* gains,
+                            double* factor, int64_t ldf, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    NNGP_REQUIRE(cov != nullptr && indices != nullptr, "pool_select_greedy: NULL cov or indices");
+    NNGP_REQUIRE(m >= 1 && count >= 0 && count <= m, "pool_select_greedy: need m >= 1 and 0 <= count <= m (m=%lld, count=%lld)",
+                 (long long)m, (long long)count);
+    NNGP_REQUIRE(ld >= m, "pool_select_greedy: ld < m (ld=%lld, m=%lld)", (long long)ld, (long long)m);
+    NNGP_REQUIRE(factor == nullptr || ldf >= m, "pool_select_greedy: ldf < m (ldf=%lld, m=%lld)", (long long)ldf, (long long)m);
+    NNGP_REQUIRE(noise >= 0.0 && noise <= 1.7976931348623157e308, "pool_select_greedy: noise must be finite and >= 0 (noise=%g)", noise);
+    if (count == 0) return 0;
+    // the two copies of d, and the factor rows when the caller keeps none
+    const size_t own = (factor == nullptr) ? (size_t)count * (size_t)m : 0;
+    double* ws = nullptr;
+    NNGP_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&ws), sizeof(double) * ((size_t)2 * (size_t)m + own), s));
+    const int rc = launch_pool_greedy(cov, m, ld, noise, count, indices, gains, own ? ws + 2 * m : factor, own ? m : ldf, ws, s);
+    NNGP_HIP_CHECK(hipFreeAsync(ws, s));
+    return rc;
+}
+
 int nngp_symv_f64(const double* a, int64_t lda, int64_t n, const double* x, double* y, double diag_add, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     NNGP_REQUIRE(a != nullptr && x != nullptr && y != nullptr && n > 0 && lda >= n, "symv_f64: bad arguments");

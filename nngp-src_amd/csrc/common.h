@@ -11,6 +11,7 @@
 #include "../../include/nngp_activations.h"
 #include "../../include/nngp_mll.h"
 #include "../../include/nngp_additive.h"
+#include "../../include/nngp_pool.h"
 
 namespace nngp {
 
@@ -465,6 +466,9 @@ int launch_rows_axpy2(double* z, double* r, const double* p, const double* q, in
 
 int launch_pool_select(const double* mean, int64_t m, int ny, const double* var, int64_t count, int biased, uint64_t seed,
                        double* key_ws, int64_t* indices, hipStream_t s);
+// pool_greedy.hip: ws holds 2 m doubles; factor [count, ldf] is the caller's or a workspace, never NULL
+int launch_pool_greedy(const double* cov, int64_t m, int64_t ld, double noise, int64_t count, int64_t* indices, double* gains,
+                       double* factor, int64_t ldf, double* ws, hipStream_t s);
 int launch_transpose_f32(const float* src, int64_t lds, float* dst, int64_t ldd, int64_t n, hipStream_t s);
 int launch_strided_copy_f64(const double* src, int64_t incs, double* dst, int64_t incd, int64_t n, hipStream_t s);
 

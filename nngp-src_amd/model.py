@@ -391,12 +391,32 @@ class GPModel:
         return mean if out is None else (mean, out)
 
 
-    def select_pool(self, x_pool, count: int, biased: bool = False, seed: int = 10):
+    def select_pool(self, x_pool, count: int, biased: bool = False, seed: int = 10, method: str = "score", return_gains: bool = False):
         """Pool scoring of the active-learning loop ON THE DEVICE (reference: active/ActiveLearner.py:43-55): predict mean and
         variance of the pool queries, score = std / max(mean), and return `count` indices -- the largest scores in ascending
         order (``np.argsort(score)[-count:]``), or, ``biased``, a score-proportional draw without replacement (Gumbel top-k on
-        the counter-based generator of synth.py, seed 10 like the reference's PRNGKey(10)).  Only the indices leave the GPU."""
+        the counter-based generator of synth.py, seed 10 like the reference's PRNGKey(10)).  Only the indices leave the GPU.
+
+        ``method="greedy"`` selects a batch instead of `count` single queries: greedy picks by conditional variance on the full
+        posterior covariance of the pool (``pool.py``, include/nngp_pool.h), each pick conditioned on the ones before it with this
+        fit's observation noise ``info()["reg"]``; the indices come in the order picked, and ``return_gains`` adds the conditional
+        variance of each pick when it was taken.  It is a rule of its own: ``biased`` cannot be combined with it."""
         import torch
+        if method not in ("score", "greedy"):
+            raise ValueError("select_pool: method must be 'score' or 'greedy', got %r" % (method,))
+        if method == "greedy":
+            if biased:
+                raise ValueError("select_pool: method='greedy' is a selection rule of its own; it has no biased draw")
+            from .pool import greedy_on_device
+            _, cov = self.predict(x_pool, cov="full", as_numpy=False)
+            m = int(cov.shape[0])
+            count = max(0, min(int(count), m))
+            if count == 0:
+                return (np.zeros(0, dtype=np.int64), np.zeros(0)) if return_gains else np.zeros(0, dtype=np.int64)
+            idx, gains, _ = greedy_on_device(self.lib, cov, count, float(self.info()["reg"]), want_gains=return_gains)
+            return (idx.cpu().numpy(), gains.cpu().numpy()) if return_gains else idx.cpu().numpy()
+        if return_gains:
+            raise ValueError("select_pool: return_gains needs method='greedy' (the score rule has no conditional variances)")
         mean, var = self.predict(x_pool, cov="diag", as_numpy=False)
         m = int(mean.shape[0])
         count = min(int(count), m)

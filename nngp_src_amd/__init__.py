@@ -14,5 +14,6 @@ __path__.insert(0, _SRC)
 from . import _lib  # noqa: E402,F401  (ctypes binding of libnngp_hip.so; loads lazily)
 from . import stax, predict, util  # noqa: E402,F401
 from .batching import batch  # noqa: E402,F401
+from .pool import pool_select_greedy  # noqa: E402,F401
 
-__all__ = ["stax", "predict", "batch", "util"]
+__all__ = ["stax", "predict", "batch", "util", "pool_select_greedy"]
