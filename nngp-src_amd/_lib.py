@@ -64,6 +64,10 @@ MAX_GROUPS = 1024
 # include/nngp_pool.h: batch-aware pool selection (greedy by conditional variance); GPU library only (no host build)
 POOL_ABI_SYMBOLS = ("nngp_pool_select_greedy",)
 
+# include/nngp_sparse.h: the sparse (inducing-point, DTC) NNGP posterior and its Gram kernel; GPU library only (no host build)
+SPARSE_ABI_SYMBOLS = ("nngp_sparse_create", "nngp_sparse_destroy", "nngp_sparse_set_inducing", "nngp_sparse_add_rows",
+                      "nngp_sparse_finish", "nngp_sparse_predict", "nngp_sparse_info", "nngp_syrk_tn_f64")
+
 
 class NngpArch(ctypes.Structure):
     _fields_ = [("n_dense", ctypes.c_int32), ("reserved", ctypes.c_int32),
@@ -85,6 +89,11 @@ class NngpFitInfo(ctypes.Structure):
     _fields_ = [("reg", ctypes.c_double), ("trace_mean", ctypes.c_double), ("rel_residual", ctypes.c_double),
                 ("refine_iters", ctypes.c_int32), ("clamped_pivots", ctypes.c_int32),
                 ("n", ctypes.c_int64), ("n_padded", ctypes.c_int64)]
+
+
+class NngpSparseInfo(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_int64), ("m", ctypes.c_int64), ("m_padded", ctypes.c_int64), ("chunks", ctypes.c_int64),
+                ("sigma2", ctypes.c_double), ("trace_mean", ctypes.c_double), ("jitter_added", ctypes.c_double)]
 
 
 class NngpError(RuntimeError):
@@ -121,6 +130,7 @@ def load(knobs: bool = False):
     bind_ard_prototypes(lib)
     bind_additive_prototypes(lib)
     bind_pool_prototypes(lib)
+    bind_sparse_prototypes(lib)
     _libs[knobs] = lib
     return lib
 
@@ -291,6 +301,23 @@ def bind_pool_prototypes(lib):
     vp, i64, dbl = ctypes.c_void_p, ctypes.c_int64, ctypes.c_double
     lib.nngp_pool_select_greedy.argtypes = [vp, i64, i64, dbl, i64, vp, vp, vp, i64, vp]
     for name in POOL_ABI_SYMBOLS:
+        getattr(lib, name).restype = ctypes.c_int
+    return lib
+
+
+def bind_sparse_prototypes(lib):
+    """Argument and result types of include/nngp_sparse.h (the HIP library only)."""
+    vp, i64, i32, dbl = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_double
+    lib.nngp_sparse_create.argtypes = [ctypes.POINTER(vp), i64, i64, i64, i32, i32, ctypes.POINTER(NngpArchAct),
+                                       ctypes.POINTER(NngpGroups), dbl, i32, dbl]
+    lib.nngp_sparse_destroy.argtypes = [vp]
+    lib.nngp_sparse_set_inducing.argtypes = [vp, vp, i64, vp]
+    lib.nngp_sparse_add_rows.argtypes = [vp, vp, vp, i64, vp]
+    lib.nngp_sparse_finish.argtypes = [vp, vp]
+    lib.nngp_sparse_predict.argtypes = [vp, vp, i64, i32, vp, vp, vp]
+    lib.nngp_sparse_info.argtypes = [vp, ctypes.POINTER(NngpSparseInfo)]
+    lib.nngp_syrk_tn_f64.argtypes = [vp, i64, vp, vp, i64, vp, i64, i64, i32, dbl, vp]
+    for name in SPARSE_ABI_SYMBOLS:
         getattr(lib, name).restype = ctypes.c_int
     return lib
 

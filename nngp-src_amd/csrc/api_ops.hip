@@ -185,6 +185,18 @@ int nngp_pool_select_greedy(const double* cov, int64_t m, int64_t ld, double noi
     return rc;
 }
 
+int nngp_syrk_tn_f64(double* c, int64_t ldc, double* r, const double* a, int64_t lda, const double* y, int64_t rows, int64_t mp,
+                     int32_t ny, double beta, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    NNGP_TRY(syrk_check(c, ldc, r, a, lda, y, rows, mp, ny, beta));
+    double* ws = nullptr;
+    const int64_t ws_doubles = syrk_ws_doubles(rows, mp);
+    NNGP_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&ws), sizeof(double) * (size_t)ws_doubles, s));
+    const int rc = launch_syrk_tn_f64(c, ldc, r, a, lda, y, rows, mp, ny, beta, ws, ws_doubles, s);
+    NNGP_HIP_CHECK(hipFreeAsync(ws, s));
+    return rc;
+}
+
 int nngp_symv_f64(const double* a, int64_t lda, int64_t n, const double* x, double* y, double diag_add, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     NNGP_REQUIRE(a != nullptr && x != nullptr && y != nullptr && n > 0 && lda >= n, "symv_f64: bad arguments");

@@ -12,6 +12,7 @@
 #include "../../include/nngp_mll.h"
 #include "../../include/nngp_additive.h"
 #include "../../include/nngp_pool.h"
+#include "../../include/nngp_sparse.h"
 
 namespace nngp {
 
@@ -53,6 +54,7 @@ void note_alloc();  // counts a device allocation (nngp_alloc_count)
 //  10  block columns from the end where key 8 = 32 issues the inverses; 11  priority of that side stream; 12  print the schedule's stream end times
 //  13  compute units the posterior solves' update grids leave to the alpha CG; 14  2 = CG iterations replayed from a hipGraph
 //  15  1 = leave-one-out gradient: C = A^-1 diag(bbar) A^-1 as one square product instead of row panels up to the diagonal (nngp_loo.hip)
+//  15  (also) 16 + mask: nngp_sparse_add_rows leaves out 1 = the cross build, 2 = the solve, 4 = the Gram kernel (stage timing, wrong results)
 #ifdef NNGP_TIMING_KNOBS
 extern std::atomic<int> g_knobs[16];
 #define NNGP_KNOB(i) (nngp::g_knobs[i].load(std::memory_order_relaxed))
@@ -469,6 +471,14 @@ int launch_pool_select(const double* mean, int64_t m, int ny, const double* var,
 // pool_greedy.hip: ws holds 2 m doubles; factor [count, ldf] is the caller's or a workspace, never NULL
 int launch_pool_greedy(const double* cov, int64_t m, int64_t ld, double noise, int64_t count, int64_t* indices, double* gains,
                        double* factor, int64_t ldf, double* ws, hipStream_t s);
+// sparse_gp.hip: C_lower [mp, mp] = beta C_lower + A^T A and (r != NULL) R [mp, ny] = beta R + A^T Y over the rows of a [rows, mp].
+// ws: ws_doubles of them, syrk_ws_doubles(rows, mp) at least or the launch is refused (-2).  The count grows with rows but is NOT
+// monotone in mp (fewer tiles, more splits): a handle that serves several mp sizes it for the largest count over all of them.
+int64_t syrk_ws_doubles(int64_t rows, int64_t mp);
+int syrk_check(const double* c, int64_t ldc, const double* r, const double* a, int64_t lda, const double* y, int64_t rows, int64_t mp,
+               int ny, double beta);  // the argument checks alone (-2), before any GPU work
+int launch_syrk_tn_f64(double* c, int64_t ldc, double* r, const double* a, int64_t lda, const double* y, int64_t rows, int64_t mp,
+                       int ny, double beta, double* ws, int64_t ws_doubles, hipStream_t s);
 int launch_transpose_f32(const float* src, int64_t lds, float* dst, int64_t ldd, int64_t n, hipStream_t s);
 int launch_strided_copy_f64(const double* src, int64_t incs, double* dst, int64_t incd, int64_t n, hipStream_t s);
 

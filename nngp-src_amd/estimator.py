@@ -19,13 +19,17 @@ from .batching import batch
 class Estimator(object):
     def __init__(self, schema_name: str, data_path: str, train_query_path: str, chunk_size: int = 64,
                  use_aux: bool = False, q_error_threshold: float = 100.0, coef_var_threshold: float = 1.0,
-                 encoder=None, kernel_type: str = "nngp", serving: bool = True, groups=None):
+                 encoder=None, kernel_type: str = "nngp", serving: bool = True, groups=None, sparse: int = 0,
+                 sparse_select: str = "greedy"):
         self.schema_name = schema_name
         self.data_path = data_path
         self.train_query_path = train_query_path
         self.chunk_size = chunk_size
         self.kernel_type = kernel_type
         self.groups = groups  # None, "pairs" or (begin, end) feature ranges: the additive kernel (stax.additive), all weights 1
+        self.sparse, self.sparse_select = int(sparse), sparse_select  # sparse > 0: serve from the inducing-point model (sparse.py)
+        if self.sparse > 0 and kernel_type != "nngp":
+            raise ValueError("sparse > 0 serves the NNGP posterior: it needs kernel_type='nngp'")
         self.serving = serving  # load_model also builds the explicit float64 inverse: predict = one product per batch
         print("loading schema and training data ... This may take seconds ...")
         if encoder is None:
@@ -47,11 +51,16 @@ class Estimator(object):
         if groups is not None:
             kernel_fn = kernel_fn.with_groups(groups)
         kernel_fn = batch(kernel_fn, device_count=0, batch_size=0)
-        self.predict_fn = nt_predict.gradient_descent_mse_ensemble(kernel_fn, self.X_train, self.Y_train, diag_reg=1e-3)
+        if self.sparse > 0:  # fitted here: every training row through the accumulation, once
+            from .sparse import sparse_mse_ensemble
+            self.predict_fn = sparse_mse_ensemble(kernel_fn, self.X_train, self.Y_train, self.sparse, diag_reg=1e-3,
+                                                  select=self.sparse_select)
+        else:
+            self.predict_fn = nt_predict.gradient_descent_mse_ensemble(kernel_fn, self.X_train, self.Y_train, diag_reg=1e-3)
 
     def load_model(self):
         model = self.predict_fn.model_for(self.kernel_type)  # kernel build + Cholesky + alpha, cached in HBM
-        if self.serving:
+        if self.serving and self.sparse <= 0:
             model.prepare_serving()
         n = self.X_train.shape[0]
         print((n, model.ny), (n, n))  # the shapes the reference prints (estimator.py:39)

@@ -61,7 +61,15 @@ def NNGP_train_and_test(args, X_train, Y_train, X_test, Y_test, query_infos_trai
         kernel_fn = kernel_fn.with_groups("pairs", full_weight=getattr(args, "additive_full_weight", 1.0))
     kernel_fn = batch(kernel_fn, device_count=0, batch_size=0)
     start = datetime.datetime.now()
-    predict_fn = nt_predict.gradient_descent_mse_ensemble(kernel_fn, X_train, Y_train, diag_reg=diag_reg)
+    if (getattr(args, "sparse", 0) or 0) > 0:  # --sparse M: every training row, M inducing rows (sparse.py)
+        from .sparse import sparse_mse_ensemble
+        if args.kernel_type != "nngp":
+            raise ValueError("--sparse serves the NNGP posterior: it needs --kernel_type nngp")
+        predict_fn = sparse_mse_ensemble(kernel_fn, X_train, Y_train, args.sparse, diag_reg=diag_reg,
+                                         select=getattr(args, "sparse_select", "greedy"),
+                                         chunk_rows=getattr(args, "sparse_chunk", 8192), jitter=getattr(args, "sparse_jitter", 1e-8))
+    else:
+        predict_fn = nt_predict.gradient_descent_mse_ensemble(kernel_fn, X_train, Y_train, diag_reg=diag_reg)
     duration = (datetime.datetime.now() - start).total_seconds()
     print('Kernel construction in %s seconds.' % duration)
 
@@ -203,14 +211,39 @@ def make_parser():
                              "(--tune_hyper and --loo work on the plain kernel only)")
     parser.add_argument("--additive_full_weight", type=float, default=1.0,
                         help="--additive: weight of the whole-input term (0 leaves it out)")
+    parser.add_argument("--sparse", type=int, default=0, metavar="M",
+                        help="fit the sparse (inducing-point) NNGP on all training rows with M inducing rows (nngp only; 0: off)")
+    parser.add_argument("--sparse_select", type=str, default="greedy", choices=("greedy", "random"),
+                        help="--sparse: how the inducing rows are chosen")
+    parser.add_argument("--sparse_chunk", type=int, default=8192, help="--sparse: training rows per accumulation step (a multiple of 128)")
+    parser.add_argument("--sparse_jitter", type=float, default=1e-8,
+                        help="--sparse: jitter on the inducing kernel, relative to its mean diagonal")
     parser.add_argument("--tune_lr", type=float, default=0.05, help="step size of --tune_hyper")
     parser.add_argument("--b_std_init", type=float, default=None, help="start of b_std for layers with b_std = 0 (--tune_hyper)")
     return parser
 
 
-if __name__ == "__main__":
-    args = make_parser().parse_args()
+def parse_args(argv=None):
+    """The command line with its conflicts checked: --sparse goes with --kernel_type nngp only, and not with --loo or --tune_*."""
+    parser = make_parser()
+    args = parser.parse_args(argv)
+    if args.sparse < 0:
+        parser.error("argument --sparse: M must be >= 0")
+    if args.sparse > 0:
+        if args.kernel_type != "nngp":
+            parser.error("argument --sparse: not allowed with --kernel_type %s (the sparse model is the NNGP posterior)" % args.kernel_type)
+        if args.loo:
+            parser.error("argument --sparse: not allowed with argument --loo")
+        if args.tune_hyper or args.tune_ard:
+            parser.error("argument --sparse: not allowed with argument --tune_hyper / --tune_ard")
+        if args.sparse_chunk < 128 or args.sparse_chunk % 128 != 0:
+            parser.error("argument --sparse_chunk: must be a positive multiple of 128")
     args.cuda = True
     args.join_query = len(args.relations.split(',')) > 1
+    return args
+
+
+if __name__ == "__main__":
+    args = parse_args()
     print(args)
     main(args)

@@ -15,5 +15,6 @@ from . import _lib  # noqa: E402,F401  (ctypes binding of libnngp_hip.so; loads 
 from . import stax, predict, util  # noqa: E402,F401
 from .batching import batch  # noqa: E402,F401
 from .pool import pool_select_greedy  # noqa: E402,F401
+from .sparse import SparseGPModel, select_inducing  # noqa: E402,F401
 
-__all__ = ["stax", "predict", "batch", "util", "pool_select_greedy"]
+__all__ = ["stax", "predict", "batch", "util", "pool_select_greedy", "SparseGPModel", "select_inducing"]
