@@ -44,6 +44,7 @@ GP_ABI_SYMBOLS = (
 # include/nngp_activations.h: networks with other activations than ReLU; GPU library only (no host build)
 ACT_ABI_SYMBOLS = ("nngp_kernel_build_act", "nngp_kernel_diag_act", "nngp_model_create_act")
 ACT_RELU, ACT_ABRELU, ACT_ERF = 0, 1, 2
+ACTIVATIONS = {"relu": (ACT_RELU, 0), "abrelu": (ACT_ABRELU, 2), "erf": (ACT_ERF, 3)}  # kind: (code, number of parameters)
 
 # include/nngp_mll.h: the NNGP marginal likelihood and its gradient; GPU library only (no host build)
 MLL_ABI_SYMBOLS = ("nngp_mll_create", "nngp_mll_destroy", "nngp_mll_set_train", "nngp_mll_evaluate", "nngp_mll_terms",
@@ -367,10 +368,9 @@ def make_arch_act(w_std, b_std, activations) -> NngpArchAct:
     if len(activations) != arch.base.n_dense - 1:
         raise ValueError("%d Dense layers need %d activations, got %d" % (arch.base.n_dense, arch.base.n_dense - 1,
                                                                           len(activations)))
-    codes = {"relu": ACT_RELU, "abrelu": ACT_ABRELU, "erf": ACT_ERF}
     for l, spec in enumerate(activations):
         spec = canonical_activation(spec)
-        arch.act[l] = codes[spec[0]]
+        arch.act[l] = ACTIVATIONS[spec[0]][0]
         for e, v in enumerate(spec[1:]):
             arch.p[l][e] = v
     return arch

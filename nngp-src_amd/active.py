@@ -21,25 +21,9 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import _lib
+from .kernel_spec import KernelSpec
 from .model import GPModel
 from .util import PredictionStatistics
-
-
-def _group_table(kernel_fn, d):
-    """None, or the checked (groups, weights, full_weight) a kernel_fn carries -- what GPModel keeps for the same arguments."""
-    groups = getattr(kernel_fn, "groups", None)
-    if groups is None:
-        return None
-    return _lib.check_groups(groups, getattr(kernel_fn, "group_weights", None), getattr(kernel_fn, "full_weight", 1.0), d=d)
-
-
-def _model_table(model):
-    return None if model.groups is None else (model.groups, model.group_weights, model.full_weight)
-
-
-def _same_scale(a, b):
-    return (a is None and b is None) or (a is not None and b is not None and np.array_equal(a, b))
 
 
 def greedy_select(cov, count, noise=0.0):
@@ -87,17 +71,13 @@ class ActiveLearner(object):
         X_train = np.ascontiguousarray(X_train, dtype=np.float64)
         Y_train = np.ascontiguousarray(Y_train, dtype=np.float64).reshape(X_train.shape[0], -1)
         n, d = X_train.shape
-        acts = getattr(kernel_fn, "activations", None)
-        scale = getattr(kernel_fn, "input_scale", None)
-        table = _group_table(kernel_fn, d)
-        if (self._model is None or _model_table(self._model) != table or not _same_scale(self._model.input_scale, scale) or self._model.n_cap < n or self._model.d != d or self._model.get != self.kernel_type
-                or self._model.activations != tuple(_lib.canonical_activation(a) for a in (acts or [("relu",)] * len(kernel_fn.w_std[1:])))):
-            if self._model is not None:
-                self._model.close()
+        spec = KernelSpec.of(kernel_fn).resolve(d)
+        m = self._model
+        if m is None or m.spec != spec or m.n_cap < n or m.d != d or m.get != self.kernel_type:
+            if m is not None:
+                m.close()
             self._fitted = None
-            self._model = GPModel(max(n, n_cap or n), d, kernel_fn.w_std, kernel_fn.b_std, get=self.kernel_type,
-                                  diag_reg=1e-3, ny=Y_train.shape[1], activations=acts, input_scale=scale,
-                                  **({} if table is None else dict(groups=table[0], group_weights=table[1], full_weight=table[2])))
+            self._model = GPModel.from_kernel_fn(spec, max(n, n_cap or n), d, get=self.kernel_type, diag_reg=1e-3, ny=Y_train.shape[1])
         # When the new training set extends the fitted one (the loop below appends the selected pool queries), only the
         # new kernel rows are built and the factor is extended (GPModel.append) instead of a full refit.
         prev = self._fitted

@@ -9,6 +9,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from .kernel_spec import ATTRIBUTES
+
 
 def batch(kernel_fn, batch_size: int = 0, device_count: int = -1, store_on_device: bool = True):
     if batch_size in (0, None) and device_count in (0, None):
@@ -28,11 +30,8 @@ def batch(kernel_fn, batch_size: int = 0, device_count: int = -1, store_on_devic
             return type(blocks[0])(*[np.concatenate([b[i] for b in blocks], axis=0) for i in range(len(blocks[0]))])
         return np.concatenate(blocks, axis=0)
 
-    for attr in ("w_std", "b_std", "n_relu", "activations", "all_relu"):
-        setattr(batched_kernel_fn, attr, getattr(kernel_fn, attr))
-    batched_kernel_fn.input_scale = getattr(kernel_fn, "input_scale", None)
-    batched_kernel_fn.groups = getattr(kernel_fn, "groups", None)
-    batched_kernel_fn.group_weights = getattr(kernel_fn, "group_weights", None)
-    batched_kernel_fn.full_weight = getattr(kernel_fn, "full_weight", 1.0)
+    spec = batched_kernel_fn.spec = kernel_fn.spec  # what the kernel is (kernel_spec.KernelSpec), and its values under their names
+    for name in ATTRIBUTES:
+        setattr(batched_kernel_fn, name, getattr(spec, name))
     batched_kernel_fn.inner = kernel_fn
     return batched_kernel_fn

@@ -131,10 +131,8 @@ class HipOps:
         import ctypes
         import torch
         from . import _lib
-        if input_scale is not None:
-            raise NotImplementedError("grid2d does not take an input_scale (per-feature relevances are single-GPU)")
-        if not _lib.all_relu(activations):  # its tile operations take the ReLU architecture only
-            raise NotImplementedError("grid2d supports Dense,(Relu,Dense)* networks only, got activations %r" % (activations,))
+        from .kernel_spec import KernelSpec
+        KernelSpec(w_std, b_std, activations, input_scale).require_plain_relu("grid2d")
         self._lib, self._ct, self.torch = _lib, ctypes, torch
         self.lib = _lib.load()
         self.device = _lib.require_gpu()

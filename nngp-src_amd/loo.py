@@ -20,6 +20,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from .kernel_spec import KernelSpec
 from .gp import F64Handle, train_hyperparameters
 from .mll import (_Params, _arch_of, _ard_terms, _relevance_arg, _reserve_ard, _train_arrays, rebuild_kernel_fn,
                   evaluate_once, finish_kernel_fn, reject_groups, relevance_groups, relevance_of, split_input_scale, tune_loop)
@@ -73,7 +74,7 @@ class LeaveOneOut(F64Handle):
         ``ard=True``): ``(value, grad, grad_s)`` as there."""
         objective, get = objective or self.objective, get or self.get
         w, b, acts = check_supported(kernel_fn_or_params, get, objective, with_grad)
-        arch = _lib.make_arch_act(w, b, acts)
+        arch = KernelSpec.of(kernel_fn_or_params).arch_act()
         val = ctypes.c_double()
         g = (ctypes.c_double * (2 * len(w) + 1))()
         if relevance is None:

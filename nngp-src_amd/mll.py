@@ -20,27 +20,20 @@ import math
 import numpy as np
 
 from . import _lib, stax
+from .kernel_spec import KernelSpec
 from .gp import F64Handle, train_hyperparameters
 
 
 def _arch_of(kernel_fn_or_params):
     """(w_std, b_std, activations) of a KernelFn (or batch() wrapper of one) or of a (w_std, b_std[, activations]) tuple."""
-    if hasattr(kernel_fn_or_params, "w_std"):
-        w, b = kernel_fn_or_params.w_std, kernel_fn_or_params.b_std
-        acts = getattr(kernel_fn_or_params, "activations", None)
-    else:
-        w, b = kernel_fn_or_params[0], kernel_fn_or_params[1]
-        acts = kernel_fn_or_params[2] if len(kernel_fn_or_params) > 2 else None
-    w = [float(v) for v in w]
-    b = [float(v) for v in b]
-    acts = [("relu",)] * (len(w) - 1) if acts is None else [_lib.canonical_activation(a) for a in acts]
-    return w, b, acts
+    spec = KernelSpec.of(kernel_fn_or_params)
+    return list(spec.w_std), list(spec.b_std), list(spec.activations)
 
 
 def reject_groups(kernel_fn_or_params, what):
     """ValueError for a kernel_fn that carries feature groups (stax.additive): the evidence and leave-one-out passes build the
     plain kernel, and the gradient with respect to the group weights does not exist yet."""
-    if getattr(kernel_fn_or_params, "groups", None) is not None:
+    if KernelSpec.of(kernel_fn_or_params).groups is not None:
         raise ValueError("%s does not cover the additive kernel over feature groups (kernel_fn.groups is set): evaluate or "
                          "tune the plain kernel_fn, then add the groups with kernel_fn.with_groups(...)" % what)
 
@@ -98,21 +91,21 @@ class NNGPMarginalLikelihood(F64Handle):
         d/dsigma_b,l^2 for every Dense layer l, then d/dlambda; None without ``with_grad``.  ``relevance`` (d values >= 0, on
         a handle made with ``ard=True``): the evidence of K(x o sqrt(s), x' o sqrt(s)), and a third result, d/ds_k (numpy, d
         values; None without ``with_grad``)."""
-        w, b, acts = _arch_of(kernel_fn_or_params)
-        arch = _lib.make_arch_act(w, b, acts)
+        spec = KernelSpec.of(kernel_fn_or_params)
+        arch = spec.arch_act()
         nlml = ctypes.c_double()
-        g = (ctypes.c_double * (2 * len(w) + 1))()
+        g = (ctypes.c_double * (2 * spec.n_dense + 1))()
         if relevance is None:
             self._check(self.lib.nngp_mll_evaluate(self._h, ctypes.byref(arch), float(diag_reg), int(bool(absolute)),
                                                    ctypes.byref(nlml), g if with_grad else None, _lib.stream_ptr()))
-            self.n_dense = len(w)
+            self.n_dense = spec.n_dense
             return nlml.value, (np.array(g[:], dtype=np.float64) if with_grad else None)
         s = self._relevance(relevance)
         gs = (ctypes.c_double * self.d)()
         self._check(self.lib.nngp_mll_evaluate_ard(self._h, ctypes.byref(arch), s, float(diag_reg), int(bool(absolute)),
                                                    ctypes.byref(nlml), g if with_grad else None, gs if with_grad else None,
                                                    _lib.stream_ptr()))
-        self.n_dense = len(w)
+        self.n_dense = spec.n_dense
         if not with_grad:
             return nlml.value, None, None
         return nlml.value, np.array(g[:], dtype=np.float64), np.array(gs[:], dtype=np.float64)
@@ -171,7 +164,7 @@ def _train_arrays(x_train, y_train):
 
 def relevance_of(kernel_fn, d):
     """The relevances input_scale^2 that a kernel_fn carries (None without an input_scale), checked against d features."""
-    scale = getattr(kernel_fn, "input_scale", None)
+    scale = KernelSpec.of(kernel_fn).input_scale
     if scale is None:
         return None
     if scale.shape[0] != d:

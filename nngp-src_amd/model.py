@@ -12,29 +12,14 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from .kernel_spec import HasSpec, KernelSpec
 
 _GET = {"nngp": _lib.GET_NNGP, "ntk": _lib.GET_NTK}
 _COV = {False: _lib.COV_NONE, None: _lib.COV_NONE, "none": _lib.COV_NONE, "diag": _lib.COV_DIAG,
         True: _lib.COV_FULL, "full": _lib.COV_FULL}
 
 
-def groups_to_fields(groups, group_weights, full_weight) -> dict:
-    """The optional checkpoint fields of a group table (none without groups)."""
-    if groups is None:
-        return {}
-    return {"groups": np.array(groups, dtype=np.int64).reshape(-1, 2), "group_weights": np.array(group_weights, dtype=np.float64),
-            "full_weight": np.array(float(full_weight))}
-
-
-def groups_from_fields(z) -> dict:
-    """GPModel's group arguments from a loaded checkpoint (empty when it has no group table)."""
-    if "groups" not in z.files:
-        return {}
-    return dict(groups=[(int(b), int(e)) for b, e in z["groups"]], group_weights=[float(v) for v in z["group_weights"]],
-                full_weight=float(z["full_weight"]))
-
-
-class GPModel:
+class GPModel(HasSpec):
     def __init__(self, n_cap: int, d: int, w_std, b_std, get: str = "nngp", diag_reg: float = 1e-3,
                  diag_reg_absolute_scale: bool = False, ny: int = 1, m_cap: int = 0, knobs: bool = False,
                  activations=None, input_scale=None, groups=None, group_weights=None, full_weight=1.0):
@@ -44,42 +29,26 @@ class GPModel:
         ``stax.KernelFn.input_scale`` does for the kernel.  groups: None, "pairs" or (begin, end) feature ranges -- the additive
         kernel full_weight K(x, x') + sum_g group_weights[g] K(x_g, x'_g) of include/nngp_additive.h (group_weights = None: all 1),
         created through nngp_model_create_additive; the input scale is applied first."""
-        from .stax import check_input_scale
-        self.input_scale = check_input_scale(input_scale)
-        if self.input_scale is not None and self.input_scale.shape[0] != int(d):
-            raise ValueError("input_scale has %d values, the model has d = %d" % (self.input_scale.shape[0], int(d)))
+        self.spec = KernelSpec(w_std, b_std, activations, input_scale, groups, group_weights, full_weight).resolve(d)
         if get not in _GET:
             raise ValueError("get must be 'nngp' or 'ntk', got %r" % (get,))
         self.lib = _lib.load(knobs)  # knobs=True: the timing-knob build (A/B tests and scripts/ only)
         self.device = _lib.require_gpu()
         self.get, self.d, self.ny, self.n_cap = get, int(d), int(ny), int(n_cap)
-        self.arch = _lib.make_arch(w_std, b_std)
-        n_hidden = self.arch.n_dense - 1
-        self.activations = tuple(_lib.canonical_activation(a) for a in (activations or [("relu",)] * n_hidden))
-        self.all_relu = _lib.all_relu(self.activations)
+        self.arch = self.spec.arch()
         self.handle = ctypes.c_void_p()
-        self.groups, self.group_weights, self.full_weight = None, None, 1.0
-        if groups is not None:
-            self.groups, self.group_weights, self.full_weight = _lib.check_groups(groups, group_weights, full_weight, d=int(d))
-            arch_act = _lib.make_arch_act(w_std, b_std, self.activations)
-            table = _lib.make_groups(self.groups, self.group_weights, self.full_weight)
-            self._check(self.lib.nngp_model_create_additive(ctypes.byref(self.handle), int(n_cap), int(m_cap), int(d), int(ny),
-                                                           ctypes.byref(arch_act), ctypes.byref(table), _GET[get],
-                                                           float(diag_reg), int(bool(diag_reg_absolute_scale))))
-        elif self.all_relu:
-            self._check(self.lib.nngp_model_create(ctypes.byref(self.handle), int(n_cap), int(m_cap), int(d), int(ny),
-                                                  ctypes.byref(self.arch), _GET[get], float(diag_reg),
-                                                  int(bool(diag_reg_absolute_scale))))
-        else:
-            arch_act = _lib.make_arch_act(w_std, b_std, self.activations)
-            self._check(self.lib.nngp_model_create_act(ctypes.byref(self.handle), int(n_cap), int(m_cap), int(d), int(ny),
-                                                      ctypes.byref(arch_act), _GET[get], float(diag_reg),
-                                                      int(bool(diag_reg_absolute_scale))))
+        self._check(self.spec.model_create(self.lib, ctypes.byref(self.handle), int(n_cap), int(m_cap), int(d), int(ny), _GET[get],
+                                           float(diag_reg), int(bool(diag_reg_absolute_scale))))
         if m_cap > 0:  # predict-side workspace now, not inside the first predict (SURVEY 8b ownership rule)
             self._check(self.lib.nngp_model_reserve(self.handle, int(m_cap), _lib.COV_DIAG))
         self.n = 0
         self._diag_reg, self._absolute = float(diag_reg), bool(diag_reg_absolute_scale)
         self._keep = []  # device tensors that must outlive asynchronous work
+
+    @classmethod
+    def from_kernel_fn(cls, kernel_fn, n_cap: int, d: int, **kwargs):
+        """The model of a ``stax`` kernel_fn (or a batch() wrapper of one, or a KernelSpec)."""
+        return cls(n_cap, d, **KernelSpec.of(kernel_fn).as_keywords(), **kwargs)
 
     def _check(self, rc: int):
         _lib.check(rc, self.lib)
@@ -119,8 +88,7 @@ class GPModel:
         self._check(self.lib.nngp_model_set_train(self.handle, _lib.ptr(xs), _lib.ptr(yd), self.n, _lib.stream_ptr()))
 
     def _scaled(self, xd):
-        from .stax import apply_input_scale
-        return apply_input_scale(self.input_scale, xd)
+        return self.spec.scale(xd)
 
     def append(self, x_new, y_new, solve: bool = True):
         """Add training rows to a fitted model: their kernel rows are built and the factor is extended in place
@@ -249,45 +217,20 @@ class GPModel:
         if self.n == 0:
             raise _lib.NngpError("save: fit the model first")
         x, y = (t.cpu().numpy() for t in self._keep)
-        w = np.array([self.arch.w_std[i] for i in range(self.arch.n_dense)])
-        b = np.array([self.arch.b_std[i] for i in range(self.arch.n_dense)])
         info = self.info()
-        extra = {}
-        if self.input_scale is not None:  # optional field of either version; a file without it loads as before
-            extra["input_scale"] = np.array(self.input_scale)
-        extra.update(groups_to_fields(self.groups, self.group_weights, self.full_weight))  # optional; a file without them loads as before
-        if not self.all_relu:  # v2: the activations as (code, a, b, c) rows; a ReLU model keeps writing v1
-            codes = {"relu": _lib.ACT_RELU, "abrelu": _lib.ACT_ABRELU, "erf": _lib.ACT_ERF}
-            extra["activations"] = np.array([[codes[a[0]]] + list(a[1:]) + [0.0] * (4 - len(a)) for a in self.activations],
-                                            dtype=np.float64).reshape(-1, 4)
-        np.savez(path, format=np.array("nngp-src_amd GPModel v1" if self.all_relu else "nngp-src_amd GPModel v2"), x=x, y=y,
-                 w_std=w, b_std=b, get=np.array(self.get),
-                 diag_reg=np.array(self._diag_reg), absolute=np.array(self._absolute), n_cap=np.array(self.n_cap),
-                 alpha=self.alpha().cpu().numpy(), reg=np.array(info["reg"]), **extra)
+        np.savez(path, x=x, y=y, get=np.array(self.get), diag_reg=np.array(self._diag_reg), absolute=np.array(self._absolute),
+                 n_cap=np.array(self.n_cap), alpha=self.alpha().cpu().numpy(), reg=np.array(info["reg"]),
+                 **self.spec.to_fields())  # format, architecture and the optional fields of the kernel
         torch.cuda.synchronize()
 
     @classmethod
     def load(cls, path: str, m_cap: int = 0, check: bool = True):
         """Rebuild a saved model on the current device; ``check``: alpha must agree with the saved one to 1e-8."""
         z = np.load(path if str(path).endswith(".npz") else str(path) + ".npz", allow_pickle=False)
-        fmt = str(z["format"])
-        if fmt not in ("nngp-src_amd GPModel v1", "nngp-src_amd GPModel v2"):
-            raise _lib.NngpError("load: %s is not a GPModel checkpoint" % path)
-        acts = None
-        if fmt.endswith("v2"):
-            names = {_lib.ACT_RELU: "relu", _lib.ACT_ABRELU: "abrelu", _lib.ACT_ERF: "erf"}
-            nparams = {"relu": 0, "abrelu": 2, "erf": 3}
-            acts = []
-            for row in z["activations"]:
-                if int(row[0]) not in names:
-                    raise _lib.NngpError("load: %s: unknown activation code %r" % (path, row[0]))
-                kind = names[int(row[0])]
-                acts.append((kind,) + tuple(float(v) for v in row[1:1 + nparams[kind]]))
+        spec = KernelSpec.from_fields(z, path)
         x, y = z["x"], z["y"]
-        grouped = groups_from_fields(z)
-        model = cls(max(int(z["n_cap"]), x.shape[0]), x.shape[1], z["w_std"].tolist(), z["b_std"].tolist(), get=str(z["get"]),
-                    diag_reg=float(z["diag_reg"]), diag_reg_absolute_scale=bool(z["absolute"]), ny=y.shape[1], m_cap=m_cap,
-                    activations=acts, input_scale=(z["input_scale"] if "input_scale" in z.files else None), **grouped)
+        model = cls.from_kernel_fn(spec, max(int(z["n_cap"]), x.shape[0]), x.shape[1], get=str(z["get"]), diag_reg=float(z["diag_reg"]),
+                                   diag_reg_absolute_scale=bool(z["absolute"]), ny=y.shape[1], m_cap=m_cap)
         model.fit(x, y)
         if check:
             a, a0 = model.alpha().cpu().numpy(), z["alpha"]

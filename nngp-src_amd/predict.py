@@ -30,18 +30,12 @@ def gradient_descent_mse_ensemble(kernel_fn, x_train, y_train, learning_rate: fl
         y_train = y_train[:, None]
     if y_train.shape[0] != x_train.shape[0]:
         raise ValueError("x_train / y_train row mismatch: %d vs %d" % (x_train.shape[0], y_train.shape[0]))
-    w_std, b_std = kernel_fn.w_std, kernel_fn.b_std
-    activations = getattr(kernel_fn, "activations", None)
-    input_scale = getattr(kernel_fn, "input_scale", None)
-    grouped = dict(groups=getattr(kernel_fn, "groups", None), group_weights=getattr(kernel_fn, "group_weights", None),
-                   full_weight=getattr(kernel_fn, "full_weight", 1.0))
     models = {}
 
     def model_for(get: str) -> GPModel:
         if get not in models:
-            m = GPModel(x_train.shape[0], x_train.shape[1], w_std, b_std, get=get, diag_reg=diag_reg,
-                        diag_reg_absolute_scale=diag_reg_absolute_scale, ny=y_train.shape[1], activations=activations,
-                        input_scale=input_scale, **grouped)
+            m = GPModel.from_kernel_fn(kernel_fn, x_train.shape[0], x_train.shape[1], get=get, diag_reg=diag_reg,
+                                       diag_reg_absolute_scale=diag_reg_absolute_scale, ny=y_train.shape[1])
             m.fit(x_train, y_train)
             models[get] = m
         return models[get]

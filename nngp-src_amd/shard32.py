@@ -36,10 +36,8 @@ class HipRowOps:
         import ctypes
         import torch
         from . import _lib
-        if input_scale is not None:
-            raise NotImplementedError("shard32 does not take an input_scale (per-feature relevances are single-GPU)")
-        if not _lib.all_relu(activations):  # its row operations take the ReLU architecture only
-            raise NotImplementedError("shard32 supports Dense,(Relu,Dense)* networks only, got activations %r" % (activations,))
+        from .kernel_spec import KernelSpec
+        KernelSpec(w_std, b_std, activations, input_scale).require_plain_relu("shard32")
         from .model import GPModel
         self._lib, self._ct, self.torch = _lib, ctypes, torch
         self.lib = _lib.load()

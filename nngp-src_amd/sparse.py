@@ -13,6 +13,7 @@ import math
 import numpy as np
 
 from . import _lib
+from .kernel_spec import HasSpec, KernelSpec
 
 _COV = {False: _lib.COV_NONE, None: _lib.COV_NONE, "none": _lib.COV_NONE, "diag": _lib.COV_DIAG, True: _lib.COV_FULL,
         "full": _lib.COV_FULL}
@@ -34,42 +35,26 @@ def check_sparse_arguments(m_cap, chunk_rows, test_cap, ny, diag_reg, jitter):
             raise ValueError("%s must be finite and >= 0, got %r" % (name, v))
 
 
-class SparseGPModel:
+class SparseGPModel(HasSpec):
     """Python owner of one ``nngp_sparse`` handle.  Keyword names and the input-scale handling follow ``GPModel``."""
 
     def __init__(self, m_cap: int, d: int, w_std, b_std, diag_reg: float = 1e-3, chunk_rows: int = 8192, jitter: float = 1e-8,
                  test_cap: int = 1024, diag_reg_absolute_scale: bool = False, ny: int = 1, activations=None, input_scale=None,
                  groups=None, group_weights=None, full_weight=1.0, knobs: bool = False):
-        from .stax import check_input_scale
         check_sparse_arguments(m_cap, chunk_rows, test_cap, ny, diag_reg, jitter)
-        self.input_scale = check_input_scale(input_scale)
-        if self.input_scale is not None and self.input_scale.shape[0] != int(d):
-            raise ValueError("input_scale has %d values, the model has d = %d" % (self.input_scale.shape[0], int(d)))
+        self.spec = KernelSpec(w_std, b_std, activations, input_scale, groups, group_weights, full_weight).resolve(d)
         self.lib = _lib.load(knobs)  # knobs=True: the timing-knob build (scripts/ only)
         self.device = _lib.require_gpu()
         self.m_cap, self.d, self.ny, self.chunk_rows = int(m_cap), int(d), int(ny), int(chunk_rows)
-        n_hidden = len(list(w_std)) - 1
-        self.activations = tuple(_lib.canonical_activation(a) for a in (activations or [("relu",)] * n_hidden))
-        arch = _lib.make_arch_act(w_std, b_std, self.activations)
-        self.groups, self.group_weights, self.full_weight = None, None, 1.0
-        table = None
-        if groups is not None:
-            self.groups, self.group_weights, self.full_weight = _lib.check_groups(groups, group_weights, full_weight, d=int(d))
-            table = _lib.make_groups(self.groups, self.group_weights, self.full_weight)
         self.handle = ctypes.c_void_p()
-        self._check(self.lib.nngp_sparse_create(ctypes.byref(self.handle), self.m_cap, self.chunk_rows, int(test_cap), self.d, self.ny,
-                                                ctypes.byref(arch), None if table is None else ctypes.byref(table), float(diag_reg),
-                                                int(bool(diag_reg_absolute_scale)), float(jitter)))
+        self._check(self.spec.sparse_create(self.lib, ctypes.byref(self.handle), self.m_cap, self.chunk_rows, int(test_cap), self.d,
+                                            self.ny, float(diag_reg), int(bool(diag_reg_absolute_scale)), float(jitter)))
         self.m = 0
 
     @classmethod
     def from_kernel_fn(cls, kernel_fn, m_cap: int, d: int, **kwargs):
-        """The model of a ``stax`` kernel_fn: its layers, activations, input scale and group table."""
-        grouped = {}
-        if getattr(kernel_fn, "groups", None) is not None:
-            grouped = dict(groups=kernel_fn.groups, group_weights=kernel_fn.group_weights, full_weight=kernel_fn.full_weight)
-        return cls(m_cap, d, kernel_fn.w_std, kernel_fn.b_std, activations=getattr(kernel_fn, "activations", None),
-                   input_scale=getattr(kernel_fn, "input_scale", None), **grouped, **kwargs)
+        """The model of a ``stax`` kernel_fn (or a batch() wrapper of one, or a KernelSpec)."""
+        return cls(m_cap, d, **KernelSpec.of(kernel_fn).as_keywords(), **kwargs)
 
     def _check(self, rc: int):
         _lib.check(rc, self.lib)
@@ -91,8 +76,7 @@ class SparseGPModel:
         return int(x.shape[0])
 
     def _device_rows(self, x):
-        from .stax import apply_input_scale
-        return apply_input_scale(self.input_scale, _lib.to_device_f64(x, self.device))
+        return self.spec.scale(_lib.to_device_f64(x, self.device))
 
     def set_inducing(self, u):
         """u [m, d], 1 <= m <= m_cap: builds and factors K_uu + jitter; forgets every training row added before."""
@@ -192,7 +176,7 @@ def select_inducing(x, m: int, kernel_fn, method: str = "greedy", candidates: in
     if n > candidates:
         cand = np.sort(np.random.RandomState(seed).choice(n, size=candidates, replace=False)).astype(np.int64)
     import torch
-    if torch.cuda.is_available() and hasattr(kernel_fn, "w_std"):
+    if torch.cuda.is_available() and hasattr(kernel_fn, "spec"):
         from .pool import greedy_on_device
         k = kernel_fn(x[cand], None, "nngp", as_numpy=False)
         idx, _, _ = greedy_on_device(_lib.load(), k, m, 0.0, want_gains=False)

@@ -13,12 +13,12 @@ parameterisation); the reference never calls them, the tests use them as a Monte
 from __future__ import annotations
 
 import collections
-import ctypes
 import math
 
 import numpy as np
 
 from . import _lib
+from .kernel_spec import HasSpec, KernelSpec
 
 Kernel = collections.namedtuple("Kernel", ["nngp", "ntk"])
 _Layer = collections.namedtuple("_Layer", ["kind", "out_dim", "w_std", "b_std", "act"], defaults=(None,))
@@ -69,73 +69,35 @@ def _phi(spec, h):
     return spec[1] * torch.special.erf(torch.from_numpy(spec[2] * h)).numpy() + spec[3]
 
 
-def check_input_scale(scale):
-    """None, or the scale as a float64 vector of finite values >= 0."""
-    if scale is None:
-        return None
-    s = np.array(scale, dtype=np.float64)
-    if s.ndim != 1 or s.shape[0] < 1 or not np.all(np.isfinite(s)) or np.any(s < 0.0):
-        raise ValueError("input_scale must be one finite value >= 0 per input feature")
-    s.setflags(write=False)
-    return s
-
-
-def apply_input_scale(scale, xd):
-    """xd [n, d] (device float64, or None) times the scale, feature by feature, on xd's device."""
-    if scale is None or xd is None:
-        return xd
-    import torch
-    if int(xd.shape[1]) != scale.shape[0]:
-        raise ValueError("input_scale has %d values, x has %d features" % (scale.shape[0], int(xd.shape[1])))
-    return xd * torch.tensor(scale, dtype=torch.float64, device=xd.device)
-
-
-class KernelFn:
-    """kernel_fn(x1, x2=None, get=None): closed-form kernel of Dense,(act,Dense)* on the GPU."""
+class KernelFn(HasSpec):
+    """kernel_fn(x1, x2=None, get=None): closed-form kernel of Dense,(act,Dense)* on the GPU.  What the kernel is lives in
+    ``.spec`` (kernel_spec.KernelSpec); its fields read as attributes of the kernel_fn."""
 
     def __init__(self, w_std, b_std, activations=None, input_scale=None, groups=None, group_weights=None, full_weight=1.0):
         """input_scale: None or d values >= 0 that multiply the features of x1 and x2 on the device before the build --
         sqrt of the relevances of include/nngp_ard.h (with_input_scale returns a copy that carries them).
         groups: None, "pairs" or (begin, end) feature ranges -- the additive kernel of include/nngp_additive.h,
         full_weight K(x, x') + sum_g group_weights[g] K(x_g, x'_g) (with_groups returns a copy that carries them)."""
-        self.input_scale = check_input_scale(input_scale)
-        if groups is None:
-            self.groups, self.group_weights, self.full_weight = None, None, 1.0
-        elif isinstance(groups, str):
-            _lib.check_groups(groups, None, full_weight, d=2)  # the name and full_weight; the table is made per call, from d
-            self.groups, self.group_weights, self.full_weight = groups, None, float(full_weight)
-            if group_weights is not None:
-                raise ValueError("groups='pairs' takes no weights: give the ranges (stax.pair_groups(d)) to weight them")
-        else:
-            self.groups, self.group_weights, self.full_weight = _lib.check_groups(groups, group_weights, full_weight)
-        self.w_std = tuple(float(w) for w in w_std)
-        self.b_std = tuple(float(b) for b in b_std)
-        self.n_relu = len(self.w_std) - 1  # hidden layers (the name is the all-ReLU one)
-        acts = [("relu",)] * self.n_relu if activations is None else list(activations)
-        if len(acts) != self.n_relu:
-            raise ValueError("%d Dense layers need %d activations" % (len(self.w_std), self.n_relu))
-        # per hidden layer: ("relu",), ("abrelu", a, b) or ("erf", a, b, c); ABRelu(0, 1) is stored as ("relu",)
-        self.activations = tuple(_lib.canonical_activation(a) for a in acts)
-        self.all_relu = _lib.all_relu(self.activations)
+        self.spec = KernelSpec(w_std, b_std, activations, input_scale, groups, group_weights, full_weight)
+
+    def _with(self, **changes):
+        return KernelFn(**self.spec.replace(**changes).as_keywords())
 
     def with_input_scale(self, scale):
         """A copy of this kernel_fn with ``input_scale = scale`` (None: without one)."""
-        return KernelFn(self.w_std, self.b_std, self.activations, scale, self.groups, self.group_weights, self.full_weight)
+        return self._with(input_scale=scale)
 
     def with_groups(self, groups, weights=None, full_weight=1.0):
         """A copy of this kernel_fn with the additive kernel over ``groups`` (None: the plain kernel again)."""
-        return KernelFn(self.w_std, self.b_std, self.activations, self.input_scale, groups, weights, full_weight)
+        return self._with(groups=groups, group_weights=weights, full_weight=full_weight)
 
     def group_table(self, d):
         """None, or (groups, weights, full_weight) checked against d features."""
-        if self.groups is None:
-            return None
-        return _lib.check_groups(self.groups, self.group_weights, self.full_weight, d=d)
+        spec = self.spec.resolve(d)
+        return None if spec.groups is None else (spec.groups, spec.group_weights, spec.full_weight)
 
     def _arch(self):
-        if self.all_relu:
-            return _lib.make_arch(self.w_std, self.b_std)
-        return _lib.make_arch_act(self.w_std, self.b_std, self.activations)
+        return self.spec.arch() if self.all_relu else self.spec.arch_act()
 
     def __call__(self, x1, x2=None, get=None, *, rows=None, as_numpy=True):
         import torch
@@ -153,24 +115,12 @@ class KernelFn:
             raise ValueError("x2 must be [N2, d] with the same d as x1")
         n1, d = int(x1d.shape[0]), int(x1d.shape[1])
         n2 = n1 if x2d is None else int(x2d.shape[0])
-        if self.input_scale is not None:
-            x1d, x2d = apply_input_scale(self.input_scale, x1d), apply_input_scale(self.input_scale, x2d)
+        x1d, x2d = self.spec.scale(x1d), self.spec.scale(x2d)
         r0, r1 = (0, n1) if rows is None else (int(rows[0]), int(rows[1]))
         outs = {g: torch.empty((n1, n2), dtype=torch.float64, device=dev) for g in set(gets)}
         if n1 > 0 and n2 > 0 and r1 > r0:
-            table = self.group_table(d)
-            if table is not None:
-                arch = _lib.make_arch_act(self.w_std, self.b_std, self.activations)
-                gr = _lib.make_groups(*table)
-                _lib.check(lib.nngp_kernel_build_additive(_lib.ptr(x1d), n1, _lib.ptr(x2d), n2, d, ctypes.byref(arch),
-                                                          ctypes.byref(gr), _lib.DTYPE_F64, _lib.ptr(outs.get("nngp")),
-                                                          _lib.ptr(outs.get("ntk")), n2, r0, r1, _lib.stream_ptr()))
-            else:
-                arch = self._arch()
-                build = lib.nngp_kernel_build if self.all_relu else lib.nngp_kernel_build_act
-                _lib.check(build(_lib.ptr(x1d), n1, _lib.ptr(x2d), n2, d, ctypes.byref(arch),
-                                                 _lib.DTYPE_F64, _lib.ptr(outs.get("nngp")), _lib.ptr(outs.get("ntk")),
-                                                 n2, r0, r1, _lib.stream_ptr()))
+            _lib.check(self.spec.kernel_build(lib, _lib.ptr(x1d), n1, _lib.ptr(x2d), n2, d, _lib.DTYPE_F64, _lib.ptr(outs.get("nngp")),
+                                              _lib.ptr(outs.get("ntk")), n2, r0, r1, _lib.stream_ptr()))
         res = {g: (t[r0:r1] if rows is not None else t) for g, t in outs.items()}
         if as_numpy:
             res = {g: t.cpu().numpy() for g, t in res.items()}

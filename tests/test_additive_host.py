@@ -116,23 +116,29 @@ def test_mll_and_loo_reject_a_grouped_kernel_fn():
 
 
 def test_checkpoint_fields_round_trip(tmp_path):
-    """The fields GPModel.save writes for a group table (model.groups_to_fields) through an .npz and back through what
-    GPModel.load reads them with (model.groups_from_fields); a checkpoint without them gives no group arguments."""
+    """The fields GPModel.save writes for a group table (KernelSpec.to_fields) through an .npz and back through what
+    GPModel.load reads them with (KernelSpec.from_fields); a checkpoint without them gives no group arguments."""
     import inspect
     from nngp_src_amd import model
+    from nngp_src_amd.kernel_spec import KernelSpec
+    w, b = [1.0, 1.0], [0.0, 0.0]
+
+    def table_of(spec):
+        return None if spec.groups is None else _lib.check_groups(spec.groups, spec.group_weights, spec.full_weight, d=7)
+
     table = _lib.check_groups(GROUPS, WEIGHTS, 0.25, d=7)
     path = str(tmp_path / "m.npz")
-    np.savez(path, x=np.zeros((2, 7)), **model.groups_to_fields(*table))
-    back = model.groups_from_fields(np.load(path, allow_pickle=False))
-    assert _lib.check_groups(back["groups"], back["group_weights"], back["full_weight"], d=7) == table
+    np.savez(path, x=np.zeros((2, 7)), **KernelSpec(w, b, None, None, *table).to_fields())
+    assert table_of(KernelSpec.from_fields(np.load(path, allow_pickle=False))) == table
     empty = _lib.check_groups([], None, 2.0, d=7)
-    np.savez(path, **model.groups_to_fields(*empty))
-    back = model.groups_from_fields(np.load(path, allow_pickle=False))
-    assert _lib.check_groups(back["groups"], back["group_weights"], back["full_weight"], d=7) == empty
-    assert model.groups_to_fields(None, None, 1.0) == {}
-    np.savez(path, x=np.zeros((2, 7)))
-    assert model.groups_from_fields(np.load(path, allow_pickle=False)) == {}
-    for fn, helper in ((model.GPModel.save, "groups_to_fields"), (model.GPModel.load, "groups_from_fields")):
+    np.savez(path, **KernelSpec(w, b, None, None, *empty).to_fields())
+    assert table_of(KernelSpec.from_fields(np.load(path, allow_pickle=False))) == empty
+    plain = KernelSpec(w, b, None, None, None, None, 1.0).to_fields()
+    assert not {"groups", "group_weights", "full_weight"} & set(plain)
+    np.savez(path, x=np.zeros((2, 7)), **plain)
+    back = KernelSpec.from_fields(np.load(path, allow_pickle=False))
+    assert (back.groups, back.group_weights, back.full_weight) == (None, None, 1.0)
+    for fn, helper in ((model.GPModel.save, "to_fields"), (model.GPModel.load, "from_fields")):
         assert helper in inspect.getsource(fn)
     params = inspect.signature(model.GPModel.__init__).parameters
     assert params["groups"].default is None and params["group_weights"].default is None and params["full_weight"].default == 1.0
