@@ -69,6 +69,12 @@ POOL_ABI_SYMBOLS = ("nngp_pool_select_greedy",)
 SPARSE_ABI_SYMBOLS = ("nngp_sparse_create", "nngp_sparse_destroy", "nngp_sparse_set_inducing", "nngp_sparse_add_rows",
                       "nngp_sparse_finish", "nngp_sparse_predict", "nngp_sparse_info", "nngp_syrk_tn_f64")
 
+# include/nngp_sparse_evidence.h: the sparse model's evidence and its gradient, on the nngp_sparse handle; GPU library only
+SPARSE_EVIDENCE_ABI_SYMBOLS = ("nngp_sparse_reserve_evidence", "nngp_sparse_set_kernel", "nngp_sparse_evidence",
+                               "nngp_sparse_evidence_grad", "nngp_sparse_evidence_terms", "nngp_sparse_adjoint_rect")
+BOUND_DTC, BOUND_VFE = 0, 1
+BOUNDS = {"dtc": BOUND_DTC, "vfe": BOUND_VFE}
+
 
 class NngpArch(ctypes.Structure):
     _fields_ = [("n_dense", ctypes.c_int32), ("reserved", ctypes.c_int32),
@@ -132,6 +138,7 @@ def load(knobs: bool = False):
     bind_additive_prototypes(lib)
     bind_pool_prototypes(lib)
     bind_sparse_prototypes(lib)
+    bind_sparse_evidence_prototypes(lib)
     _libs[knobs] = lib
     return lib
 
@@ -319,6 +326,21 @@ def bind_sparse_prototypes(lib):
     lib.nngp_sparse_info.argtypes = [vp, ctypes.POINTER(NngpSparseInfo)]
     lib.nngp_syrk_tn_f64.argtypes = [vp, i64, vp, vp, i64, vp, i64, i64, i32, dbl, vp]
     for name in SPARSE_ABI_SYMBOLS:
+        getattr(lib, name).restype = ctypes.c_int
+    return lib
+
+
+def bind_sparse_evidence_prototypes(lib):
+    """Argument and result types of include/nngp_sparse_evidence.h (the HIP library only)."""
+    vp, i64, i32, dbl = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_double
+    pd, archp = ctypes.POINTER(dbl), ctypes.POINTER(NngpArchAct)
+    lib.nngp_sparse_reserve_evidence.argtypes = [vp]
+    lib.nngp_sparse_set_kernel.argtypes = [vp, archp, dbl, i32]
+    lib.nngp_sparse_evidence.argtypes = [vp, i32, pd, vp]
+    lib.nngp_sparse_evidence_grad.argtypes = [vp, vp, vp, i64, i32, pd, pd, vp]
+    lib.nngp_sparse_evidence_terms.argtypes = [vp, pd, i32]
+    lib.nngp_sparse_adjoint_rect.argtypes = [vp, i64, vp, i64, i32, archp, vp, i64, vp, vp, pd, vp]
+    for name in SPARSE_EVIDENCE_ABI_SYMBOLS:
         getattr(lib, name).restype = ctypes.c_int
     return lib
 

@@ -18,7 +18,9 @@
 //                     the same bits.  The launch boundary between the two kernels is the only synchronisation: no workgroup
 //                     waits for another, there is no counter and no cooperative launch, so nothing here can hang.
 //   k_sparse_*        the small passes of the model: jitter and padding of K_uu, the trace, B = sigma2 I + G, R^T, the predict finish.
-#include "gp_f64.h"
+// The handle itself is in sparse_gp.h: the model's evidence (sparse_evidence.hip) works on it too, and add_rows keeps the sums the
+// evidence needs (y^T y, the per-layer sums of q) beside its own.
+#include "sparse_gp.h"
 
 #include <algorithm>
 #include <vector>
@@ -330,53 +332,13 @@ using namespace nngp;
 // ---------------------------------------------------------------------------------------------------------------------------
 // C ABI (include/nngp_sparse.h)
 
-struct nngp_sparse {
-    int64_t m_cap = 0, mp_cap = 0, chunk_rows = 0, test_cap = 0;
-    int d = 0, ny = 1;
-    ArchDev arch{};
-    GroupsDev groups{};
-    double diag_reg = 0.0, jitter = 0.0;
-    int absolute = 0;
-
-    int64_t m = 0, mp = 0;       // m = 0: no inducing set
-    int64_t n = 0, chunks = 0;
-    bool finished = false;
-    double sigma2 = 0.0;         // host copy of scal[2] after a finish
-
-    double* u = nullptr;         // [m_cap, d]
-    double* uq = nullptr;        // [m_cap] |u|^2 / d
-    double* lu = nullptr;        // [mp, mp] K_uu -> L_u
-    double* gm = nullptr;        // [mp, mp] G, lower tiles
-    double* lb = nullptr;        // [mp, mp] B -> L_B
-    double* dinv_u = nullptr;    // [mp, 128]
-    double* dinv_b = nullptr;
-    double* rm = nullptr;        // [mp, ny] R
-    double* ct = nullptr;        // [128, mp]: R^T, solved in place to C^T
-    double* chunk = nullptr;     // [chunk_rows, mp] K(X_c, U) -> Vt
-    double* pt = nullptr;        // [test_cap, mp] K(X_t, U) -> P
-    double* qt = nullptr;        // [test_cap, mp] Q
-    double* xq = nullptr;        // [max(chunk_rows, test_cap)] |x|^2 / d of a chunk / test block
-    double* kd = nullptr;        // [same] K(x, x)
-    double* t = nullptr;         // [t_rows, 128] solve scratch
-    int64_t t_rows = 0;
-    double* ws = nullptr;        // split partials of the Gram kernel: ws_doubles, enough for every mp up to mp_cap
-    int64_t ws_doubles = 0;
-    double* scal = nullptr;      // [4]: sum K_ii, jitter added, sigma2
-    int* status = nullptr;
-    // full covariance only (grown on first use)
-    int64_t full_cap = 0;
-    double* fp = nullptr;        // [full_cap, mp_cap]
-    double* fq = nullptr;
-    double* fc = nullptr;        // [full_cap, full_cap]
-    double* fxq = nullptr;       // [full_cap]
-};
-
 namespace {
 
 void sparse_free(nngp_sparse* h) {
     for (double** p : {&h->u, &h->uq, &h->lu, &h->gm, &h->lb, &h->dinv_u, &h->dinv_b, &h->rm, &h->ct, &h->chunk, &h->pt, &h->qt, &h->xq,
                        &h->kd, &h->t, &h->ws, &h->scal, &h->fp, &h->fq, &h->fc, &h->fxq})
         dev_free(*p);
+    sparse_evidence_free(h);
     dev_free(h->status);
     groups_destroy(&h->groups);
 }
@@ -402,9 +364,9 @@ int sparse_alloc(nngp_sparse* h) {
     // set_inducing may choose any mp <= mp_cap, and a smaller mp can need more (fewer tiles, so more splits of each): the largest
     for (int64_t q = ST; q <= mp; q += ST) h->ws_doubles = std::max(h->ws_doubles, syrk_ws_doubles(h->chunk_rows, q));
     NNGP_TRY(dev_alloc(&h->ws, h->ws_doubles));
-    NNGP_TRY(dev_alloc(&h->scal, 4));
+    NNGP_TRY(dev_alloc(&h->scal, kSpScal));
     NNGP_TRY(dev_alloc(&h->status, 1));
-    NNGP_HIP_CHECK(hipMemset(h->scal, 0, sizeof(double) * 4));
+    NNGP_HIP_CHECK(hipMemset(h->scal, 0, sizeof(double) * kSpScal));
     return 0;
 }
 
@@ -413,28 +375,6 @@ int sparse_alloc(nngp_sparse* h) {
 inline int sparse_skip() {
     const int k = NNGP_KNOB(15);
     return k >= 16 ? k - 16 : 0;
-}
-
-// out [rp, mp] <- K(x [rows, d], U) L_u^-T: zero, cross build, solve in place.  rp = rows rounded up to 128.
-int sparse_cross(nngp_sparse* h, const double* x, const double* xq, int64_t rows, double* out, hipStream_t s, int skip = 0) {
-    const int64_t mp = h->mp, rp = round_up(rows, TB);
-    NNGP_HIP_CHECK(hipMemsetAsync(out, 0, sizeof(double) * rp * mp, s));
-    BuildArgs b{};
-    b.x1 = x;
-    b.x2 = h->u;
-    b.q1 = xq;
-    b.q2 = h->uq;
-    b.n1 = rows;
-    b.n2 = h->m;
-    b.d = h->d;
-    b.row_begin = 0;
-    b.row_end = rows;
-    b.sym = 0;
-    b.nngp64 = out;
-    b.ld64 = b.ld32 = mp;
-    if (!(skip & 1)) NNGP_TRY(launch_kernel_build(b, h->arch, s));
-    if (skip & 2) return 0;
-    return trsm_fwd_f64(out, mp, rp, h->lu, mp, h->dinv_u, mp, h->t, false, s);
 }
 
 int sparse_full_reserve(nngp_sparse* h, int64_t mt, hipStream_t s) {
@@ -458,6 +398,30 @@ int sparse_full_reserve(nngp_sparse* h, int64_t mt, hipStream_t s) {
 }
 
 }  // namespace
+
+namespace nngp {
+// out [rp, mp] <- K(x [rows, d], U) L_u^-T: zero, cross build, solve in place.  rp = rows rounded up to 128.
+int sparse_cross(nngp_sparse* h, const double* x, const double* xq, int64_t rows, double* out, hipStream_t s, int skip) {
+    const int64_t mp = h->mp, rp = round_up(rows, TB);
+    NNGP_HIP_CHECK(hipMemsetAsync(out, 0, sizeof(double) * rp * mp, s));
+    BuildArgs b{};
+    b.x1 = x;
+    b.x2 = h->u;
+    b.q1 = xq;
+    b.q2 = h->uq;
+    b.n1 = rows;
+    b.n2 = h->m;
+    b.d = h->d;
+    b.row_begin = 0;
+    b.row_end = rows;
+    b.sym = 0;
+    b.nngp64 = out;
+    b.ld64 = b.ld32 = mp;
+    if (!(skip & 1)) NNGP_TRY(launch_kernel_build(b, h->arch, s));
+    if (skip & 2) return 0;
+    return trsm_fwd_f64(out, mp, rp, h->lu, mp, h->dinv_u, mp, h->t, false, s);
+}
+}  // namespace nngp
 
 extern "C" {
 
@@ -533,7 +497,7 @@ int nngp_sparse_set_inducing(nngp_sparse* h, const double* u, int64_t m, void* s
     b.nngp64 = h->lu;
     b.ld64 = b.ld32 = mp;
     NNGP_TRY(launch_kernel_build(b, h->arch, s));
-    NNGP_HIP_CHECK(hipMemsetAsync(h->scal, 0, sizeof(double) * 4, s));
+    NNGP_HIP_CHECK(hipMemsetAsync(h->scal, 0, sizeof(double) * kSpScal, s));
     hipLaunchKernelGGL(k_sparse_jitter, dim3(1), dim3(256), 0, s, h->lu, mp, m, mp, h->jitter, h->scal);
     NNGP_HIP_CHECK(hipGetLastError());
     NNGP_TRY(potrf_f64(h->lu, mp, mp, h->dinv_u, h->status, s));
@@ -558,6 +522,7 @@ int nngp_sparse_add_rows(nngp_sparse* h, const double* x, const double* y, int64
         NNGP_TRY(launch_kernel_diag(xc, h->xq, c, h->d, h->arch, h->kd, nullptr, s));
         hipLaunchKernelGGL(k_sparse_trace, dim3(1), dim3(256), 0, s, h->kd, c, h->scal);
         NNGP_HIP_CHECK(hipGetLastError());
+        NNGP_TRY(sparse_evidence_sums(h, h->xq, y + r0 * h->ny, c, s));
         const int skip = sparse_skip();
         NNGP_TRY(sparse_cross(h, xc, h->xq, c, h->chunk, s, skip));
         if (!(skip & 4))

@@ -4,6 +4,9 @@ The exact models hold the N x N kernel; ``SparseGPModel`` keeps every label, sum
 pays O(N m^2) once and O(m^2) per served query with variance.  Training rows arrive in any number of calls and are uploaded
 chunk by chunk, so X never has to fit on the device at once.  ``select_inducing`` chooses the inducing rows: greedy by
 conditional variance of the prior kernel (``nngp_pool_select_greedy``), or at random.
+
+The model's evidence and its gradient (``include/nngp_sparse_evidence.h``) tune W_std / b_std / diag_reg at the N the sparse model
+is for: ``SparseGPModel.evidence`` / ``evidence_grad``, the evaluator ``SparseEvidence`` and ``tune_hyperparameters``.
 """
 from __future__ import annotations
 
@@ -46,6 +49,7 @@ class SparseGPModel(HasSpec):
         self.lib = _lib.load(knobs)  # knobs=True: the timing-knob build (scripts/ only)
         self.device = _lib.require_gpu()
         self.m_cap, self.d, self.ny, self.chunk_rows = int(m_cap), int(d), int(ny), int(chunk_rows)
+        self.absolute = bool(diag_reg_absolute_scale)
         self.handle = ctypes.c_void_p()
         self._check(self.spec.sparse_create(self.lib, ctypes.byref(self.handle), self.m_cap, self.chunk_rows, int(test_cap), self.d,
                                             self.ny, float(diag_reg), int(bool(diag_reg_absolute_scale)), float(jitter)))
@@ -142,10 +146,82 @@ class SparseGPModel(HasSpec):
             torch.cuda.current_stream().synchronize()  # xt goes out of scope
         return mean if out is None else (mean, out)
 
+    # ---- the evidence (include/nngp_sparse_evidence.h) ----
+    def reserve_evidence(self):
+        """Allocate what the evidence's gradient needs (nngp_sparse_reserve_evidence); the evidence calls after it allocate nothing."""
+        check_evidence_spec(self.spec)
+        self._check(self.lib.nngp_sparse_reserve_evidence(self.handle))
+        return self
+
+    def set_kernel(self, kernel_fn_or_params, diag_reg, diag_reg_absolute_scale=None):
+        """New W_std / b_std / activations (the same number of Dense layers) and diag_reg on this handle, without reallocation.
+        Forgets the inducing rows and the training rows: set_inducing, add_rows and finish follow."""
+        spec = check_evidence_spec(KernelSpec.of(kernel_fn_or_params))
+        if spec.n_dense != self.spec.n_dense:
+            raise ValueError("the model was created for %d Dense layers, got %d" % (self.spec.n_dense, spec.n_dense))
+        if diag_reg_absolute_scale is not None:
+            self.absolute = bool(diag_reg_absolute_scale)
+        self._check(self.lib.nngp_sparse_set_kernel(self.handle, ctypes.byref(spec.arch_act()), float(diag_reg), int(self.absolute)))
+        self.spec = spec.replace(input_scale=self.spec.input_scale, groups=self.spec.groups, group_weights=self.spec.group_weights,
+                                 full_weight=self.spec.full_weight)
+        self.m = 0
+        return self
+
+    def evidence(self, bound="vfe"):
+        """The negative log evidence of the fitted model (after finish; ny = 1): ``"dtc"``, or Titsias' collapsed bound ``"vfe"``."""
+        nlml = ctypes.c_double()
+        self._check(self.lib.nngp_sparse_evidence(self.handle, bound_code(bound), ctypes.byref(nlml), _lib.stream_ptr()))
+        return nlml.value
+
+    def evidence_grad(self, x, y, bound="vfe"):
+        """(nlml, grad): x, y are the rows that were added, handed again.  grad (numpy, 2 n_dense + 1 values): d/dsigma_w,l^2,
+        d/dsigma_b,l^2 for every Dense layer l, then d/dlambda, with the inducing rows held fixed."""
+        code = bound_code(bound)
+        xd = _lib.to_device_f64(x, self.device)
+        n = self._rows(xd, "x")
+        xd = self._device_rows(xd)
+        yd = _lib.to_device_f64(y, self.device).reshape(-1)
+        if int(yd.shape[0]) != n:
+            raise ValueError("y must have one value per row of x (%d), got %s" % (n, tuple(yd.shape)))
+        nlml = ctypes.c_double()
+        g = (ctypes.c_double * (2 * self.spec.n_dense + 1))()
+        self._check(self.lib.nngp_sparse_evidence_grad(self.handle, _lib.ptr(xd), _lib.ptr(yd), n, code, ctypes.byref(nlml), g,
+                                                       _lib.stream_ptr()))  # synchronises: xd, yd may go
+        return nlml.value, np.array(g[:], dtype=np.float64)
+
+    def evidence_terms(self):
+        """Of the last evidence_grad (nngp_sparse_evidence_terms): ``quad[p]``, ``trace[p]`` with grad = -quad / 2 + trace / 2, and
+        the scalar sums."""
+        nc = 2 * self.spec.n_dense
+        count = 2 * (nc + 1) + 7
+        out = (ctypes.c_double * count)()
+        self._check(self.lib.nngp_sparse_evidence_terms(self.handle, out, count))
+        v = np.array(out[:], dtype=np.float64)
+        t = v[2 * (nc + 1):]
+        return {"quad": v[0:2 * (nc + 1):2], "trace": v[1:2 * (nc + 1):2], "logdet_half": t[0], "yy_cc": t[1], "tr_kff": t[2],
+                "tr_g": t[3], "sigma2": t[4], "tr_binv": t[5], "b_b": t[6]}
+
     def info(self) -> dict:
         fi = _lib.NngpSparseInfo()
         self._check(self.lib.nngp_sparse_info(self.handle, ctypes.byref(fi)))
         return {k: getattr(fi, k) for k, _ in fi._fields_}
+
+
+def bound_code(bound):
+    if bound not in _lib.BOUNDS:
+        raise ValueError("bound must be 'vfe' or 'dtc', got %r" % (bound,))
+    return _lib.BOUNDS[bound]
+
+
+def check_evidence_spec(spec):
+    """ValueError for what the sparse evidence does not cover: feature groups and an input_scale."""
+    if spec.groups is not None:
+        raise ValueError("the sparse evidence does not cover the additive kernel over feature groups (groups is set): "
+                         "tune the plain kernel_fn, then add the groups with kernel_fn.with_groups(...)")
+    if spec.input_scale is not None:
+        raise ValueError("the sparse evidence does not cover an input_scale (per-feature relevances): scale the rows first "
+                         "and tune the kernel_fn without it")
+    return spec
 
 
 def greedy_rows(cov, count: int):
@@ -217,3 +293,76 @@ def sparse_mse_ensemble(kernel_fn, x_train, y_train, m: int, diag_reg: float = 1
     predict_fn.model_for = model_for
     predict_fn.inducing = inducing
     return predict_fn
+
+
+class SparseEvidence:
+    """The sparse evidence of (x, y) with fixed inducing rows as an evaluator of ``mll.tune_loop``: every ``evaluate`` runs
+    set_kernel -> set_inducing -> add_rows -> finish -> evidence[_grad] on one handle, with the rows kept on the device.
+    ``inducing``: the rows themselves [m, d], or indices into x."""
+
+    def __init__(self, x, y, inducing, bound="vfe", chunk_rows: int = 8192, jitter: float = 1e-8):
+        bound_code(bound)
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        inducing = np.asarray(inducing)
+        if inducing.ndim == 1:
+            inducing = x[inducing.astype(np.int64)]
+        self.device = _lib.require_gpu()
+        self.x, self.u = _lib.to_device_f64(x, self.device), _lib.to_device_f64(inducing, self.device)
+        self.y = _lib.to_device_f64(np.asarray(y, dtype=np.float64).reshape(-1), self.device)
+        if self.x.ndim != 2 or int(self.x.shape[0]) != int(self.y.shape[0]) or int(self.u.shape[1]) != int(self.x.shape[1]):
+            raise ValueError("x must be [N, d] with one y per row and inducing rows of d features")
+        self.bound, self.jitter = bound, float(jitter)
+        self.chunk_rows = min(int(chunk_rows), -(-int(self.x.shape[0]) // 128) * 128)
+        self.model = None
+
+    def evaluate(self, params, diag_reg=1e-3, absolute=False, with_grad=True):
+        """(nlml, grad) at ``params`` = a kernel_fn or (w_std, b_std, activations); grad is None without ``with_grad``."""
+        spec = check_evidence_spec(KernelSpec.of(params))
+        if self.model is None:
+            self.model = SparseGPModel(int(self.u.shape[0]), int(self.x.shape[1]), diag_reg=diag_reg, chunk_rows=self.chunk_rows,
+                                       jitter=self.jitter, test_cap=128, diag_reg_absolute_scale=absolute,
+                                       **spec.as_keywords()).reserve_evidence()
+        self.model.set_kernel(spec, diag_reg, absolute).set_inducing(self.u).add_rows(self.x, self.y).finish()
+        if with_grad:
+            return self.model.evidence_grad(self.x, self.y, self.bound)
+        return self.model.evidence(self.bound), None
+
+    def terms(self):
+        return self.model.evidence_terms()
+
+    def close(self):
+        if self.model is not None:
+            self.model.close()
+            self.model = None
+
+
+def tune_hyperparameters(kernel_fn, x_train, y_train, m: int, bound: str = "vfe", select: str = "greedy", steps: int = 50,
+                         lr: float = 0.05, b_std_init=None, min_diag_reg: float = 1e-6, report=print, evaluator=None,
+                         diag_reg: float = 1e-3, diag_reg_absolute_scale: bool = False, chunk_rows: int = 8192,
+                         jitter: float = 1e-8, candidates: int = 16384, seed: int = 10, inducing=None):
+    """``mll.tune_hyperparameters`` on the sparse evidence: adaptive gradient steps over log sigma_w,l^2, log sigma_b,l^2 and
+    log lambda, at O(N m^2) per step instead of O(N^3).  The m inducing rows are chosen once, by ``select_inducing`` with the
+    starting kernel (or given as ``inducing``: indices into x_train), and held fixed.  ``bound``: ``"vfe"`` (Titsias' collapsed
+    bound) or ``"dtc"``.  Reports ``"Step: %d, neg marginal likelihood: %f"`` after each step.  Returns ``(kernel_fn_tuned,
+    diag_reg_tuned, history)``, ready for ``sparse_mse_ensemble``.  ``evaluator``: an object with ``evaluate(params, diag_reg,
+    absolute, with_grad)`` to use instead of the GPU (tests drive the same loop with the NumPy reference); it brings its own
+    inducing rows.  A kernel_fn with feature groups or an input_scale is refused."""
+    from . import mll
+    bound_code(bound)
+    w0, b0, acts = mll.check_supported(kernel_fn)
+    check_evidence_spec(KernelSpec.of(kernel_fn))
+    x, y = mll._train_arrays(x_train, y_train)
+    params = mll._Params(w0, b0, diag_reg, b_std_init, min_diag_reg)
+    own = evaluator is None
+    if own:
+        if inducing is None:
+            m = min(int(m), x.shape[0])
+            inducing = select_inducing(x, m, kernel_fn, method=select, candidates=max(int(candidates), m), seed=seed)
+        evaluator = SparseEvidence(x, y, inducing, bound=bound, chunk_rows=chunk_rows, jitter=jitter)
+    try:
+        raw, history = mll.tune_loop(params, evaluator, acts, diag_reg_absolute_scale, steps, lr, report)
+    finally:
+        if own:
+            evaluator.close()
+    w, b, lam, _ = params.unpack(raw)
+    return mll.rebuild_kernel_fn(w, b, acts), lam, history

@@ -153,6 +153,19 @@ def tune_kernel_fn(args, X_train, Y_train):
     return kernel_fn, diag_reg
 
 
+def sparse_tune_kernel_fn(args, X_train, Y_train):
+    """--sparse_tune STEPS (with --sparse M): W_std / b_std / diag_reg by the sparse model's own evidence (sparse.py), at the N
+    the sparse model is for."""
+    from . import sparse
+    _, _, kernel_fn = kernel_fn_from_args(args)
+    kernel_fn, diag_reg, _ = sparse.tune_hyperparameters(
+        kernel_fn, X_train, Y_train, args.sparse, bound=getattr(args, "sparse_bound", "vfe"),
+        select=getattr(args, "sparse_select", "greedy"), steps=args.sparse_tune, lr=args.tune_lr, b_std_init=args.b_std_init,
+        chunk_rows=getattr(args, "sparse_chunk", 8192), jitter=getattr(args, "sparse_jitter", 1e-8))
+    print("Tuned W_std={} b_std={} diag_reg={}".format(list(kernel_fn.w_std), list(kernel_fn.b_std), diag_reg))
+    return kernel_fn, diag_reg
+
+
 def main(args):
     tune = getattr(args, "tune_hyper", 0) or 0
     if tune and args.kernel_type != 'nngp':
@@ -171,6 +184,10 @@ def main(args):
         from .gp import GP_train_and_test
         return GP_train_and_test(X_train, Y_train, X_test, Y_test, qi_train, qi_test,
                                  cov="full" if getattr(args, "full_cov", False) else "diag", pred_stat=pred_stat)
+    if (getattr(args, "sparse_tune", 0) or 0) > 0:
+        kernel_fn, diag_reg = sparse_tune_kernel_fn(args, X_train, Y_train)
+        return NNGP_train_and_test(args, X_train, Y_train, X_test, Y_test, qi_train, qi_test, kernel_fn=kernel_fn,
+                                   diag_reg=diag_reg)
     if tune:
         kernel_fn, diag_reg = tune_kernel_fn(args, X_train, Y_train)
         return NNGP_train_and_test(args, X_train, Y_train, X_test, Y_test, qi_train, qi_test, kernel_fn=kernel_fn,
@@ -218,17 +235,26 @@ def make_parser():
     parser.add_argument("--sparse_chunk", type=int, default=8192, help="--sparse: training rows per accumulation step (a multiple of 128)")
     parser.add_argument("--sparse_jitter", type=float, default=1e-8,
                         help="--sparse: jitter on the inducing kernel, relative to its mean diagonal")
+    parser.add_argument("--sparse_tune", type=int, default=0, metavar="STEPS",
+                        help="--sparse: steps of tuning W_std / b_std / diag_reg on the sparse model's evidence before the fit (0: off)")
+    parser.add_argument("--sparse_bound", type=str, default="vfe", choices=("vfe", "dtc"),
+                        help="--sparse_tune: the objective, Titsias' collapsed bound (vfe) or the DTC evidence")
     parser.add_argument("--tune_lr", type=float, default=0.05, help="step size of --tune_hyper")
     parser.add_argument("--b_std_init", type=float, default=None, help="start of b_std for layers with b_std = 0 (--tune_hyper)")
     return parser
 
 
 def parse_args(argv=None):
-    """The command line with its conflicts checked: --sparse goes with --kernel_type nngp only, and not with --loo or --tune_*."""
+    """The command line with its conflicts checked: --sparse goes with --kernel_type nngp only, and not with --loo or --tune_*;
+    --sparse_tune needs --sparse."""
     parser = make_parser()
     args = parser.parse_args(argv)
     if args.sparse < 0:
         parser.error("argument --sparse: M must be >= 0")
+    if args.sparse_tune < 0:
+        parser.error("argument --sparse_tune: STEPS must be >= 0")
+    if args.sparse_tune > 0 and args.sparse <= 0:
+        parser.error("argument --sparse_tune: needs --sparse M (it tunes the sparse model's evidence)")
     if args.sparse > 0:
         if args.kernel_type != "nngp":
             parser.error("argument --sparse: not allowed with --kernel_type %s (the sparse model is the NNGP posterior)" % args.kernel_type)
