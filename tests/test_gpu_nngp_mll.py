@@ -68,6 +68,8 @@ CASES = [  # n, n_dense, W_std, b_std, absolute, rows
     (4097, 4, 1.0, 0.05, True, "synthetic"),
     (1000, 2, 1.0, 0.0, False, "centred"),
     (1000, 4, 1.5, 0.05, False, "centred"),
+    (127, 5, 1.5, 0.05, False, "centred"),   # 5 .. 8 Dense layers: the NLC = 8 instantiation of the adjoint pass
+    (127, 9, 1.2, 0.05, True, "unit"),       # 9 .. 16 Dense layers: NLC = 16
 ]
 
 

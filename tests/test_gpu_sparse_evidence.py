@@ -114,11 +114,15 @@ def test_exact_limit_against_the_exact_evidence_on_the_device(golden_dir, net):
 
 @pytest.mark.parametrize("c,m,d", [(65, 63, 33), (130, 128, 20)])
 @pytest.mark.parametrize("net", [([1.2, 0.9], [0.05, 0.0], [("relu",)]),
-                                 ([1.2, 0.9, 1.1, 1.0], [0.0, 0.1, 0.02, 0.05], [("relu",), ("abrelu", 0.1, 1.0), ("relu",)])])
+                                 ([1.2, 0.9, 1.1, 1.0], [0.0, 0.1, 0.02, 0.05], [("relu",), ("abrelu", 0.1, 1.0), ("relu",)]),
+                                 # 5 and 9 Dense layers: the NLC = 8 and NLC = 16 instantiations of the pass
+                                 ([1.2, 0.9, 1.1, 1.0, 1.3], [0.0, 0.1, 0.02, 0.05, 0.0], [("relu",), ("abrelu", 0.1, 1.0)] * 2),
+                                 ([1.2, 1.1] * 4 + [1.0], [0.0, 0.05, 0.0] * 3, [("relu",)] * 7 + [("abrelu", 0.1, 1.0)])])
 def test_rectangular_adjoint_pass_alone(c, m, d, net):
     """A random dense seed (NaN beyond its m logical columns) and a random rank-one seed against the reference's contraction with
     the forward-mode tangents.  Bound: 1e-12 sum_ij |seed_ij dK_ij| -- the kernel build's documented 3e-14 per entry and layer, at
-    most three hidden layers and the two factors of the reverse sweep, a factor 5 over their sum."""
+    most three hidden layers and the two factors of the reverse sweep, a factor 5 over their sum (a factor 2 for the eight hidden
+    layers of the deepest network; per entry the pass is held far tighter in test_gpu_adjoint_angles.py)."""
     rng = np.random.default_rng(c + m)
     x, u = rng.standard_normal((c, d)), rng.standard_normal((m, d))
     u[3] = x[7]  # a training row that is also an inducing row takes the general formula
