@@ -312,11 +312,21 @@ def _ds(s, e):
     return max(up, dn)
 
 
-def entry(k, q1, q2, net, c0, exact_diag=False, extras=(0.0,)):
+def _mpf(v):
+    return v if isinstance(v, mp.mpf) else mp.mpf(float(v))
+
+
+def entry(k, q1, q2, net, c0, exact_diag=False, extras=(0.0,), initial=0, kk_exact=False):
     """One entry from float64 (k, q1, q2): (K, T, [gK per extra], [gT per extra]) -- the referee's values and the carried
     angle allowances (absolute, without C1).  extras: further roundings of rr in units of u rho^2 (1: an unfused q q' product,
-    the float64 oracle's; 0: the gate a device result is held to)."""
-    state = (mp.mpf(float(k)), mp.mpf(float(q1)), mp.mpf(float(q2)), mp.mpf(0))
+    the float64 oracle's; 0: the gate a device result is held to).
+    For the additive build (tests/additive_angle_reference.py; the defaults leave every other caller's numbers as they were):
+    k, q1, q2 may be mpmath numbers -- the exact rationals S / width of a slice whose width is no power of two -- and initial
+    counts the roundings the device has put into each of them before the first Dense layer (2: the rounded reciprocal and the
+    product with it; a count of operations in the code, not a measurement).  kk_exact: leave the term u k^2 out of E where it
+    stands for nothing -- the first layer behind an exact Dense layer on exact inputs, when k k is a float64 number, so that
+    fma(q, q', -(k k)) rounds once, the exact bracket (exactly collinear small integers: E = 0, theta = 0 or pi exactly)."""
+    state = (_mpf(k), _mpf(q1), _mpf(q2), mp.mpf(0))
     if exact_diag:
         state = (state[1], state[1], state[1], mp.mpf(0))
     trace = []
@@ -324,7 +334,7 @@ def entry(k, q1, q2, net, c0, exact_diag=False, extras=(0.0,)):
     gk, gt = [mp.mpf(0)] * len(extras), [mp.mpf(0)] * len(extras)
     if exact_diag:
         return kk, tt, gk, gt
-    ek = eq = 0  # roundings carried by k (units of u rho) and by q, q' (relative) into layer l
+    ek = eq = initial  # roundings carried by k (units of u rho) and by q, q' (relative) into layer l
     for l in range(net.nd - 1):
         info = trace[l][4]
         ek, eq = ek + _dense_count(net, l), eq + _dense_count(net, l)
@@ -333,7 +343,7 @@ def entry(k, q1, q2, net, c0, exact_diag=False, extras=(0.0,)):
             if info[0] == "erf":
                 assert l == 0, "the Erf allowance counts the roundings of one Dense layer on exact inputs"
                 _, u, w, r, rho2, bb = info
-                dc = _dense_count(net, l)
+                dc = _dense_count(net, l) + initial
                 dw = (bb * bb * 4 * dc * U * rho2 + (dc + 3) * U * r) / (2 * r)
                 dth = c0 + abs(u) * w / (u * u + w * w) * ((dc + 2) * U + dw)
                 if x > 0:  # nothing of the extras applies to an Erf layer
@@ -343,7 +353,10 @@ def entry(k, q1, q2, net, c0, exact_diag=False, extras=(0.0,)):
                 _, kl, sl, rho2 = info
                 dth = mp.mpf(c0)
                 if rho2 > 0:
-                    e = U * (kl * kl + 2 * ek * abs(kl) * mp.sqrt(rho2) + (2 * eq + extra) * rho2)
+                    k2r = kl * kl  # the rounding of k k
+                    if kk_exact and ek == 0 and eq == 0 and mp.mpf(float(kl)) == kl and mp.mpf(float(kl) * float(kl)) == k2r:
+                        k2r = 0
+                    e = U * (k2r + 2 * ek * abs(kl) * mp.sqrt(rho2) + (2 * eq + extra) * rho2)
                     dth = dth + abs(kl) * _ds(sl, e) / rho2
             dk = dt = mp.mpf(0)
             for sg in (1, -1):

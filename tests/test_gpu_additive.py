@@ -2,13 +2,18 @@
 float64 reference (additive_reference.py), the bits of the _act entry points without groups, and the fit / append / predict /
 serving / pool / checkpoint / CLI stack of a model created by nngp_model_create_additive.
 
-The kernel gate is the one tests/test_gpu_activations.py applies to nngp_kernel_build_act: max |got - want| <= 1e-11 max |want| for
-float64 outputs and 1e-6 for float32 ones, with the entries at which q q' - k^2 is pure rounding noise held to 1e-6.  There that
-means two rows that are the same vector, because the reference has no exact form for them.  Here the reference gives a term whose
-two slices are bit-identical its diagonal form (additive_reference.kernel_fn, exact_same), so those entries -- the diagonal and
-the forest defaults -- are held to 1e-11 like any other; 1e-6 is left for the entries at which some term sees two slices that
-are collinear WITHOUT being identical (antiparallel, scaled, every pair of a width-1 group: additive_reference.degenerate),
-where reference and kernel both take the square root of rounding noise, up to sqrt(2^-52) = 1.5e-8 of angle."""
+The kernel gate of THIS file is the one tests/test_gpu_activations.py applies to nngp_kernel_build_act: max |got - want| <=
+1e-11 max |want| for float64 outputs and 1e-6 for float32 ones, against a float64 reference on random and forest rows.  A term whose
+two slices are bit-identical takes its diagonal form in the reference too (additive_reference.kernel_fn, exact_same) and is held
+to 1e-11; the entries at which some term sees two slices that are collinear WITHOUT being identical (antiparallel, scaled, every
+pair of a width-1 group: additive_reference.degenerate) are held to 1e-6 here, because on these inputs the float64 reference takes
+the square root of the Gram product's rounding noise, up to sqrt(2^-52) = 1.5e-8 of angle, and cannot say more.
+That rule is a limit of this file's reference, not of the kernel.  Those entries -- and every other entry, each on the scale of its
+own sqrt(K_ii K_jj) and not of the matrix's largest -- are held tightly in tests/test_gpu_additive_angles.py: rows with exactly
+representable Gram entries (q q' - k^2 is exactly 0 on the device and in the referee when the slices are exactly collinear), an
+mpmath referee per group, a per-entry gate of a few 1e-16 of scale plus the carried angle allowance; of the 2151 entries of its
+width-1 block this file's rule would leave 1791 at 1e-6, where the gate there is 8e-16 of max |want|.  Angles over [0, pi] inside a
+group, identical slices on different rows and group boundaries against the staged chunks are covered there as well."""
 import contextlib
 import ctypes
 import io
