@@ -45,8 +45,28 @@ int nngp_rbf_gp_kernel(const double* x1, int64_t n1, const double* x2, int64_t n
  * above the diagonal blocks is workspace, read the lower triangle only). */
 int nngp_rbf_gp_factor_buffer(const nngp_rbf_gp* gp, double** l, int64_t* ld, int64_t* n_padded);
 /* Blocked lower Cholesky of a float64 matrix in place (n multiple of 128, ld >= n even); the lower triangle receives L.
- * A pivot that is not positive returns rc < 0 with a message naming the column; nothing is clamped.  Synchronises. */
+ * A pivot that is not positive returns rc < 0 with a message naming the column; nothing is clamped.  Synchronises.
+ * The strict upper triangle of the input is never read.  On return the part above the 128 x 128 diagonal blocks is
+ * workspace (inside the diagonal blocks the upper triangle is zero): read the lower triangle only. */
 int nngp_potrf_f64(double* a, int64_t n, int64_t ld, void* stream);
+
+/* ---- the float64 core on its own: what every float64 model above and in nngp_mll.h / nngp_sparse.h factors and solves with ----
+ * The same factorisation, keeping the inverted diagonal blocks: dinv [n, 128], block kb at dinv + kb * 128 * 128 holds
+ * L_kk^-1 (lower, zero above the diagonal), which every panel and every solve multiplies by. */
+int nngp_potrf_dinv_f64(double* a, int64_t n, int64_t ld, double* dinv, void* stream);
+/* bt [rows, ldb] <- bt L^-T in place (each row b becomes L^-1 b), with l [n, ldl] and dinv as nngp_potrf_dinv_f64 left them.
+ * rows and n are multiples of 128, ldb and ldl even and >= n, the pointers 16-byte aligned.  tri != 0: bt holds the identity
+ * (rows == n), the result L^-T is upper triangular and only the rows down to the end of each column's diagonal block are
+ * written; the rest of bt is not touched.  The rows x 128 scratch is allocated and freed in stream order. */
+int nngp_trsm_fwd_f64(double* bt, int64_t ldb, int64_t rows, const double* l, int64_t ldl, const double* dinv, int64_t n, int32_t tri,
+                      void* stream);
+/* The evaluation sequence of the models on a caller's matrix: a [n, lda] (lower triangle read), y [n], any n >= 1, padded
+ * inside to Np = n rounded up to 128 with the identity.  mode 0: L and w = L^-1 y; mode 1: also L^-T, A^-1 = L^-T L^-1,
+ * alpha = A^-1 y and neg_rowsq = -diag(A^-1); mode 2: as mode 1 without the A^-1 product.  alpha has the same bits in modes 1
+ * and 2, with or without neg_rowsq.  Outputs (each may be NULL): l, zt, ainv [Np, Np]; w, alpha, neg_rowsq [Np].  An output
+ * the mode does not produce must be NULL (rc < 0).  Allocates and frees its workspace; synchronises. */
+int nngp_factor_solve_f64(const double* a, int64_t lda, const double* y, int64_t n, int32_t mode, double* l, double* w, double* zt,
+                          double* ainv, double* alpha, double* neg_rowsq, void* stream);
 
 #ifdef __cplusplus
 }

@@ -38,6 +38,7 @@ ABI_SYMBOLS = (
 GP_ABI_SYMBOLS = (
     "nngp_rbf_gp_create", "nngp_rbf_gp_destroy", "nngp_rbf_gp_set_train", "nngp_rbf_gp_evaluate", "nngp_rbf_gp_terms",
     "nngp_rbf_gp_predict", "nngp_rbf_gp_kernel", "nngp_rbf_gp_factor_buffer", "nngp_potrf_f64",
+    "nngp_potrf_dinv_f64", "nngp_trsm_fwd_f64", "nngp_factor_solve_f64",
 )
 
 
@@ -236,6 +237,9 @@ def bind_gp_prototypes(lib):
     lib.nngp_rbf_gp_kernel.argtypes = [vp, i64, vp, i64, i32, dbl, vp, i64, vp]
     lib.nngp_rbf_gp_factor_buffer.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(i64), ctypes.POINTER(i64)]
     lib.nngp_potrf_f64.argtypes = [vp, i64, i64, vp]
+    lib.nngp_potrf_dinv_f64.argtypes = [vp, i64, i64, vp, vp]
+    lib.nngp_trsm_fwd_f64.argtypes = [vp, i64, i64, vp, i64, vp, i64, i32, vp]
+    lib.nngp_factor_solve_f64.argtypes = [vp, i64, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp]
     for name in GP_ABI_SYMBOLS:
         getattr(lib, name).restype = ctypes.c_int
     return lib

@@ -35,6 +35,76 @@ int nngp_potrf_f64(double* a, int64_t n, int64_t ld, void* stream) {
     return rc;
 }
 
+int nngp_potrf_dinv_f64(double* a, int64_t n, int64_t ld, double* dinv, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    NNGP_REQUIRE(a != nullptr && dinv != nullptr && n > 0 && n % TB == 0, "potrf_dinv_f64: n must be a positive multiple of %d (n=%lld)", TB,
+                 (long long)n);
+    NNGP_REQUIRE(((uintptr_t)dinv & 15) == 0, "potrf_dinv_f64: dinv must be 16-byte aligned");
+    int* status = nullptr;
+    NNGP_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&status), sizeof(int), s));
+    int rc = potrf_f64(a, n, ld, dinv, status, s);
+    if (rc == 0) rc = potrf_f64_status(status, s, "potrf_dinv_f64");
+    (void)hipFreeAsync(status, s);
+    return rc;
+}
+
+int nngp_trsm_fwd_f64(double* bt, int64_t ldb, int64_t rows, const double* l, int64_t ldl, const double* dinv, int64_t n, int32_t tri,
+                      void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    NNGP_REQUIRE(bt != nullptr && l != nullptr && dinv != nullptr, "trsm_fwd_f64: NULL argument");
+    NNGP_REQUIRE(rows > 0 && n > 0 && rows % TB == 0 && n % TB == 0, "trsm_fwd_f64: rows, n must be positive multiples of %d (rows=%lld n=%lld)",
+                 TB, (long long)rows, (long long)n);
+    NNGP_REQUIRE(tri == 0 || rows == n, "trsm_fwd_f64: the triangular mode solves the identity, rows must equal n (rows=%lld n=%lld)",
+                 (long long)rows, (long long)n);
+    // what the GEMMs inside would reject after the first launches: said here, before any
+    NNGP_REQUIRE(ldb >= n && ldl >= n && ldb % 2 == 0 && ldl % 2 == 0, "trsm_fwd_f64: ldb, ldl must be >= n and even (ldb=%lld ldl=%lld n=%lld)",
+                 (long long)ldb, (long long)ldl, (long long)n);
+    NNGP_REQUIRE((((uintptr_t)bt | (uintptr_t)l | (uintptr_t)dinv) & 15) == 0, "trsm_fwd_f64: operands must be 16-byte aligned");
+    double* t = nullptr;
+    NNGP_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&t), sizeof(double) * (size_t)rows * TB, s));
+    const int rc = trsm_fwd_f64(bt, ldb, rows, l, ldl, dinv, n, t, tri != 0, s);
+    (void)hipFreeAsync(t, s);
+    return rc;
+}
+
+namespace {
+// the body of nngp_factor_solve_f64 on its workspace (the caller frees it whatever happens here)
+int factor_solve_on(GpWorkspace* w, const double* a, int64_t lda, const double* y, int64_t n, int mode, double* l, double* wout,
+                    double* zt, double* ainv, double* alpha, double* neg_rowsq, hipStream_t s) {
+    const int64_t np = round_up(n, TB);
+    NNGP_TRY(ws_alloc(w, n, 1, 1, 1, np));
+    NNGP_TRY(ws_set_train(w, y, y, hipMemcpyDeviceToDevice, n, s));  // no inputs here: y stands in for the n x 1 "x"
+    hipLaunchKernelGGL(k_eye, dim3((unsigned)((np + 255) / 256), (unsigned)np), dim3(256), 0, s, w->a, np, np);
+    NNGP_HIP_CHECK(hipGetLastError());
+    NNGP_HIP_CHECK(hipMemcpy2DAsync(w->a, sizeof(double) * np, a, sizeof(double) * lda, sizeof(double) * n, n, hipMemcpyDeviceToDevice, s));
+    NNGP_TRY(factor_and_solve(w, mode, "factor_solve_f64", s, mode == kGpSolveW ? nullptr : neg_rowsq));
+    const size_t vec = sizeof(double) * np, mat = vec * np;
+    if (l) NNGP_HIP_CHECK(hipMemcpyAsync(l, w->a, mat, hipMemcpyDeviceToDevice, s));
+    if (wout) NNGP_HIP_CHECK(hipMemcpyAsync(wout, w->wrow, vec, hipMemcpyDeviceToDevice, s));
+    if (zt) NNGP_HIP_CHECK(hipMemcpyAsync(zt, w->zt, mat, hipMemcpyDeviceToDevice, s));
+    if (ainv) NNGP_HIP_CHECK(hipMemcpyAsync(ainv, w->ainv, mat, hipMemcpyDeviceToDevice, s));
+    if (alpha) NNGP_HIP_CHECK(hipMemcpyAsync(alpha, w->alpha, vec, hipMemcpyDeviceToDevice, s));
+    NNGP_HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
+}
+}  // namespace
+
+int nngp_factor_solve_f64(const double* a, int64_t lda, const double* y, int64_t n, int32_t mode, double* l, double* w, double* zt,
+                          double* ainv, double* alpha, double* neg_rowsq, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    NNGP_REQUIRE(a != nullptr && y != nullptr && n >= 1 && lda >= n, "factor_solve_f64: need a, y, n >= 1 and lda >= n (n=%lld lda=%lld)",
+                 (long long)n, (long long)lda);
+    NNGP_REQUIRE(mode == kGpSolveW || mode == kGpSolveInverse || mode == kGpSolveRows, "factor_solve_f64: unknown mode %d", (int)mode);
+    NNGP_REQUIRE(mode != kGpSolveW || (zt == nullptr && alpha == nullptr && neg_rowsq == nullptr),
+                 "factor_solve_f64: mode 0 produces L and w only");
+    NNGP_REQUIRE(mode == kGpSolveInverse || ainv == nullptr, "factor_solve_f64: only mode 1 produces A^-1");
+    GpWorkspace ws;
+    const int rc = factor_solve_on(&ws, a, lda, y, n, mode, l, w, zt, ainv, alpha, neg_rowsq, s);
+    if (rc != 0) (void)hipStreamSynchronize(s);
+    ws_free(&ws);
+    return rc;
+}
+
 int nngp_gemm_nt_f32(float* c, int64_t ldc, const float* a, int64_t lda, const float* b, int64_t ldb, int64_t m,
                      int64_t n, int64_t k, float alpha, float beta, int32_t lower_only, void* stream) {
     NNGP_REQUIRE(a != nullptr && b != nullptr && c != nullptr, "gemm_nt_f32: NULL argument");

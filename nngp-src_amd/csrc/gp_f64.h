@@ -1,5 +1,5 @@
 // The float64 exact-GP core of the RBF GP (rbf_gp.hip) and the NNGP marginal likelihood (nngp_mll.hip): the blocked Cholesky and
-// triangular solves (gp_f64.hip, also behind nngp_potrf_f64 in api_ops.hip), the evidence workspace both models hold with the
+// triangular solves (gp_f64.hip, also behind nngp_potrf_f64 and the three core operators of api_ops.hip), the evidence workspace both models hold with the
 // evaluation sequence they share, and the device helpers of their lower-tile passes and fixed-order finish kernels.
 #pragma once
 #include "model.h"
@@ -12,6 +12,8 @@ int potrf_f64_status(const int* status, hipStream_t s, const char* who);  // syn
 // B^T (r rows of length np) <- B^T L^-T (tri: B^T is the identity); t: r x 128 scratch
 int trsm_fwd_f64(double* bt, int64_t ldb, int64_t r, const double* l, int64_t ldl, const double* dinv, int64_t np, double* t,
                  bool tri, hipStream_t s);
+// a [n, ld] <- the identity (grid: (n + 255) / 256 by n)
+__global__ __launch_bounds__(256) void k_eye(double* a, int64_t ld, int64_t n);
 // per row: dot[row] = dot_add + sum_k m[row, k] v[k];  sq[row] = sq_from - sum_k m[row, k]^2  (either may be NULL)
 __global__ __launch_bounds__(256) void k_rowdot(const double* m, int64_t ld, int64_t cols, const double* v, double* dot,
                                                double dot_add, double* sq, double sq_from);

@@ -127,6 +127,55 @@ def trsm(b, l, dinv):
     torch.cuda.synchronize()
 
 
+def _padded_f64(a, ld, fill=float("nan")):
+    """numpy [r, c] -> cuda [r, ld] float64 with the padding columns filled (they are never read)."""
+    a = np.asarray(a, dtype=np.float64)
+    t = torch.full((a.shape[0], ld), fill, dtype=torch.float64, device=dev())
+    t[:, :a.shape[1]] = torch.from_numpy(np.ascontiguousarray(a)).to(dev())
+    return t
+
+
+def potrf_dinv_f64(a, ld=None):
+    """nngp_potrf_dinv_f64 on a copy of a [n, n] with leading dimension ld: (rc, what came back in a's place [n, n] -- L in the
+    lower triangle, workspace above the diagonal blocks --, dinv [n / 128, 128, 128]).  rc < 0: lib.nngp_last_error() says why."""
+    lib = _lib.load()
+    n = a.shape[0]
+    ad = _padded_f64(a, n if ld is None else ld)
+    dinv = torch.full((n // 128, 128, 128), float("nan"), dtype=torch.float64, device=dev())
+    rc = lib.nngp_potrf_dinv_f64(_lib.ptr(ad), n, ad.stride(0), _lib.ptr(dinv), _lib.stream_ptr())
+    torch.cuda.synchronize()
+    return rc, ad[:, :n].cpu().numpy(), dinv.cpu().numpy()
+
+
+def trsm_fwd_f64(bt, l, dinv, tri=False, ldb=None, ldl=None):
+    """nngp_trsm_fwd_f64 on a copy of bt [rows, n]: bt L^-T."""
+    lib = _lib.load()
+    rows, n = bt.shape
+    bd = _padded_f64(bt, n if ldb is None else ldb)
+    ld_ = _padded_f64(l, n if ldl is None else ldl)
+    dd = _lib.to_device_f64(dinv, dev())
+    _lib.check(lib.nngp_trsm_fwd_f64(_lib.ptr(bd), bd.stride(0), rows, _lib.ptr(ld_), ld_.stride(0), _lib.ptr(dd), n, int(tri),
+                                     _lib.stream_ptr()), lib)
+    torch.cuda.synchronize()
+    return bd[:, :n].cpu().numpy()
+
+
+def factor_solve_f64(a, y, mode, want=("l", "w", "zt", "ainv", "alpha", "nrs"), lda=None):
+    """nngp_factor_solve_f64: the outputs named in want that the mode produces, as numpy arrays of the padded size."""
+    lib = _lib.load()
+    n = a.shape[0]
+    np_ = -(-n // 128) * 128
+    made = {0: ("l", "w"), 1: ("l", "w", "zt", "ainv", "alpha", "nrs"), 2: ("l", "w", "zt", "alpha", "nrs")}[mode]
+    ad = _padded_f64(a, n if lda is None else lda)
+    yd = _lib.to_device_f64(y, dev())
+    out = {k: torch.full((np_, np_) if k in ("l", "zt", "ainv") else (np_,), float("nan"), dtype=torch.float64, device=dev())
+           for k in want if k in made}
+    _lib.check(lib.nngp_factor_solve_f64(_lib.ptr(ad), ad.stride(0), _lib.ptr(yd), n, mode, *[_lib.ptr(out.get(k)) for k in
+                                         ("l", "w", "zt", "ainv", "alpha", "nrs")], _lib.stream_ptr()), lib)
+    torch.cuda.synchronize()
+    return {k: t.cpu().numpy() for k, t in out.items()}
+
+
 def rel_l2(a, b):
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
     return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
