@@ -2,6 +2,7 @@
 // what tests/, scripts/ and the multi-GPU drivers call directly.
 #include "model.h"
 #include "gp_f64.h"
+#include "../../include/nngp_i8s.h"
 
 extern "C" {
 
@@ -220,6 +221,135 @@ int nngp_gemm_nt_i8s(double* c, int64_t ldc, const double* cin, int64_t ldcin, c
                                 pl.ndiag, sca, scb, m, n, s);
     (void)hipStreamSynchronize(s);
     (void)hipFree(ws);
+    return rc;
+}
+
+// ---- include/nngp_i8s.h: the launches of the int8 residual pipeline without a model object (tests/test_gpu_i8s.py) ----
+// i8s_cut_planes and i8s_product_rows (api_predict.hip) take their buffers, events, timers and the alpha CG's gate from nngp_model;
+// the operators below issue the same launch_i8s_* / launch_gemm_nt_i8s calls in the same order on a workspace of their own.
+int nngp_i8s_cut_rows(const double* src, int64_t ld, int64_t rows, int64_t cols, int32_t ns, const double* scale_in, double* scale_out,
+                      int8_t* planes, int64_t ldp, double* writeback, void* stream) {
+    NNGP_REQUIRE(src != nullptr && planes != nullptr && (scale_in != nullptr || scale_out != nullptr), "i8s_cut_rows: NULL argument");
+    NNGP_REQUIRE(ns >= 2 && ns <= 7, "i8s_cut_rows: 2..7 planes (ns=%d)", (int)ns);
+    NNGP_REQUIRE(rows > 0 && cols > 0 && ld >= cols && ld % 2 == 0, "i8s_cut_rows: ld must be even and >= cols (rows=%lld cols=%lld ld=%lld)",
+                 (long long)rows, (long long)cols, (long long)ld);
+    NNGP_REQUIRE(ldp >= round_up(cols, 128) && ldp % 16 == 0, "i8s_cut_rows: ldp must be a multiple of 16 and >= cols rounded up to 128 (ldp=%lld)",
+                 (long long)ldp);
+    NNGP_REQUIRE((((uintptr_t)src | (uintptr_t)planes | (uintptr_t)writeback) & 15) == 0, "i8s_cut_rows: operands must be 16-byte aligned");
+    return launch_i8s_slice_rows(src, ld, rows, cols, ns, scale_in, scale_out, planes, ldp, rows * ldp, (hipStream_t)stream, writeback);
+}
+
+int nngp_i8s_cut_sym(const double* src, int64_t ld, int64_t n, int32_t ns, double* scale_out, int8_t* planes, int64_t ldp,
+                     int32_t by_rows, double* sqsum, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    NNGP_REQUIRE(src != nullptr && planes != nullptr && scale_out != nullptr, "i8s_cut_sym: NULL argument");
+    NNGP_REQUIRE(by_rows != 0 ? (ns >= 2 && ns <= 7) : (ns == 5 || ns == 7), "i8s_cut_sym: 5 or 7 planes (by rows: 2..7) (ns=%d)", (int)ns);
+    NNGP_REQUIRE(n > 0 && n % TB == 0 && ld >= n && ld % 2 == 0, "i8s_cut_sym: n must be a positive multiple of %d, ld even and >= n (n=%lld ld=%lld)",
+                 TB, (long long)n, (long long)ld);
+    NNGP_REQUIRE(ldp >= n && ldp % 16 == 0, "i8s_cut_sym: ldp must be a multiple of 16 and >= n (ldp=%lld)", (long long)ldp);
+    NNGP_REQUIRE((((uintptr_t)src | (uintptr_t)planes) & 15) == 0, "i8s_cut_sym: operands must be 16-byte aligned");
+    NNGP_TRY(launch_i8s_diag_bound_scale(src, ld, n, scale_out, s));
+    if (by_rows != 0)
+        NNGP_TRY(launch_i8s_slice_rows(src, ld, n, n, ns, scale_out, nullptr, planes, ldp, n * ldp, s));
+    else
+        NNGP_TRY(launch_i8s_slice_sym(src, ld, n, ns, scale_out, planes, ldp, n * ldp, s));
+    if (sqsum != nullptr) NNGP_TRY(launch_i8s_scale_sqsum(scale_out, n, sqsum, s));
+    return 0;
+}
+
+namespace {
+struct I8sResidualWs {  // one allocation, carved up
+    int8_t *kplanes, *zplanes;
+    double *kscale, *zscale, *rowpart;
+    int32_t* partial;
+    int* counters;
+};
+
+int i8s_residual_on(const I8sResidualWs& w, const I8Plan& pl, double* out, int64_t ldo, const double* cin, int64_t ldcin, double* z, int64_t ldz,
+                    const double* kmat, int64_t ldk, int64_t mp, int64_t n, double alpha, double beta, double gamma, int ns_z, int ns_k,
+                    bool round_z, bool sym, float* out32, const double* base, double* var, double* delta, double* zstat,
+                    double* floor_rows, double* floor_z, hipStream_t s) {
+    const int64_t kr = round_up(n, 256), zr = round_up(mp, 256);
+    // the kernel matrix's planes: scales from the diagonal, no pass over the matrix (i8s_cut_planes)
+    NNGP_TRY(launch_i8s_diag_bound_scale(kmat, ldk, n, w.kscale, s));
+    if (sym)
+        NNGP_TRY(launch_i8s_slice_sym(kmat, ldk, n, ns_k, w.kscale, w.kplanes, n, kr * n, s));
+    else
+        NNGP_TRY(launch_i8s_slice_rows(kmat, ldk, n, n, ns_k, w.kscale, nullptr, w.kplanes, n, kr * n, s));
+    NNGP_TRY(launch_i8s_scale_sqsum(w.kscale, n, w.kscale + n, s));
+    // z's planes, the exact plane products, the combination (i8s_product_rows)
+    const int64_t nchunk = i8s_chunks(n, &pl), slab = mp * n;
+    NNGP_TRY(launch_i8s_slice_rows(z, ldz, mp, n, ns_z, nullptr, w.zscale, w.zplanes, n, zr * n, s, round_z ? z : nullptr));
+    NNGP_TRY(launch_gemm_nt_i8s(w.partial, n, slab, w.zplanes, n, zr * n, w.kplanes, n, kr * n, pl, mp, n, n, w.counters, 0, s));
+    I8Fuse fuse;
+    fuse.out32 = out32;
+    fuse.ld32 = n;
+    fuse.part = w.rowpart;
+    NNGP_TRY(launch_i8s_combine(out, ldo, cin, ldcin, beta, alpha, z, ldz, gamma, w.partial, n, slab, (int)nchunk, pl.ndiag, w.zscale,
+                                w.kscale, mp, n, s, out32 != nullptr ? &fuse : nullptr));
+    if (out32 != nullptr) {
+        NNGP_TRY(launch_i8s_rowstat_finish(w.rowpart, n, mp, base, var, delta, zstat, s));
+        if (floor_rows != nullptr) {
+            NNGP_HIP_CHECK(hipMemsetAsync(floor_rows, 0, sizeof(double), s));
+            NNGP_TRY(launch_i8s_floor_ratio_rows(zstat, mp, var, pl, ns_z, ns_k, w.kscale + n, reinterpret_cast<unsigned long long*>(floor_rows), s));
+        }
+        if (floor_z != nullptr) {
+            NNGP_HIP_CHECK(hipMemsetAsync(floor_z, 0, sizeof(double), s));
+            NNGP_TRY(launch_i8s_floor_ratio(z, ldz, mp, n, var, pl, ns_z, ns_k, w.kscale + n, reinterpret_cast<unsigned long long*>(floor_z), s));
+        }
+    }
+    return 0;
+}
+}  // namespace
+
+int nngp_i8s_residual(double* out, int64_t ldo, const double* cin, int64_t ldcin, double* z, int64_t ldz, const double* kmat,
+                      int64_t ldk, int64_t mp, int64_t n, double alpha, double beta, double gamma, int32_t ns_z, int32_t ns_k,
+                      int32_t cut, int32_t round_z, int32_t sym, float* out32, const double* base, double* var, double* delta,
+                      double* zstat, double* floor_rows, double* floor_z, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    NNGP_REQUIRE(out != nullptr && z != nullptr && kmat != nullptr && (beta == 0.0 || cin != nullptr), "i8s_residual: NULL argument");
+    NNGP_REQUIRE(mp > 0 && n > 0 && mp % TB == 0 && n % TB == 0, "i8s_residual: mp, n must be positive multiples of %d (mp=%lld n=%lld)", TB,
+                 (long long)mp, (long long)n);
+    NNGP_REQUIRE(ns_z >= 2 && ns_z <= 7 && ns_k >= 2 && ns_k <= 7, "i8s_residual: 2..7 planes per operand (ns_z=%d ns_k=%d)", (int)ns_z, (int)ns_k);
+    NNGP_REQUIRE(cut >= 0, "i8s_residual: cut must be >= 0 (cut=%d)", (int)cut);
+    NNGP_REQUIRE(sym == 0 || ns_k == 5 || ns_k == 7, "i8s_residual: the symmetric cut makes 5 or 7 planes (ns_k=%d)", (int)ns_k);
+    NNGP_REQUIRE(ldo >= n && ldz >= n && ldk >= n && (cin == nullptr || ldcin >= n) && ldo % 2 == 0 && ldz % 2 == 0 && ldk % 2 == 0 &&
+                     (cin == nullptr || ldcin % 2 == 0),
+                 "i8s_residual: leading dimensions must be even and >= n (ldo=%lld ldcin=%lld ldz=%lld ldk=%lld)", (long long)ldo,
+                 (long long)ldcin, (long long)ldz, (long long)ldk);
+    NNGP_REQUIRE((((uintptr_t)out | (uintptr_t)cin | (uintptr_t)z | (uintptr_t)kmat | (uintptr_t)out32) & 15) == 0,
+                 "i8s_residual: operands must be 16-byte aligned");
+    const bool any = out32 || base || var || delta || zstat, all = out32 && base && var && delta && zstat;
+    NNGP_REQUIRE(any == all, "i8s_residual: the fused outputs (out32, base, var, delta, zstat) come all or none");
+    NNGP_REQUIRE(!all || cin != nullptr, "i8s_residual: the fused outputs need cin");
+    NNGP_REQUIRE(all || (floor_rows == nullptr && floor_z == nullptr), "i8s_residual: the floor ratios need the fused outputs");
+    I8Plan pl;
+    NNGP_TRY(i8s_plan(ns_z, ns_k, cut, &pl));
+    const int64_t kr = round_up(n, 256), zr = round_up(mp, 256), nchunk = i8s_chunks(n, &pl);
+    const size_t kp_bytes = (size_t)(ns_k * kr * n), zp_bytes = (size_t)(ns_z * zr * n);
+    const size_t part_bytes = (size_t)(nchunk * pl.ndiag * mp * n) * sizeof(int32_t);
+    const size_t f64s = (size_t)(n + 2) + (size_t)mp + (size_t)(mp * i8s_col_blocks(n) * 4);
+    NNGP_REQUIRE(part_bytes < (size_t)16 << 30, "i8s_residual: the test entry keeps all partial products (16 GB limit)");
+    char* ws = nullptr;
+    NNGP_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&ws), kp_bytes + zp_bytes + part_bytes + sizeof(double) * f64s + 64, s));
+    I8sResidualWs w;
+    w.kplanes = reinterpret_cast<int8_t*>(ws);
+    w.zplanes = w.kplanes + kp_bytes;
+    w.partial = reinterpret_cast<int32_t*>(ws + kp_bytes + zp_bytes);
+    w.kscale = reinterpret_cast<double*>(ws + kp_bytes + zp_bytes + part_bytes);
+    w.zscale = w.kscale + n + 2;
+    w.rowpart = w.zscale + mp;
+    w.counters = reinterpret_cast<int*>(w.rowpart + mp * i8s_col_blocks(n) * 4);
+    int rc = 0;
+    // rows up to the next multiple of 256 are read by the product (never stored): zero planes, as ensure_i8s leaves them
+    if (hipMemsetAsync(ws, 0, kp_bytes + zp_bytes, s) != hipSuccess || hipMemsetAsync(w.counters, 0, 64, s) != hipSuccess) {
+        nngp::set_error("i8s_residual: hipMemsetAsync failed");
+        rc = -1;
+    }
+    if (rc == 0)
+        rc = i8s_residual_on(w, pl, out, ldo, cin, ldcin, z, ldz, kmat, ldk, mp, n, alpha, beta, gamma, ns_z, ns_k, round_z != 0, sym != 0,
+                             out32, base, var, delta, zstat, floor_rows, floor_z, s);
+    (void)hipFreeAsync(ws, s);
     return rc;
 }
 

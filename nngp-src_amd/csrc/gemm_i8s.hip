@@ -44,11 +44,21 @@ constexpr int kI8ChunkBlocks3 = 320;  // ... when no diagonal has more than 3 pa
 // ---- row scales ----
 // A power of two (integers stay exact, and the scaling itself never rounds): with max|row| = f 2^e, f in [0.5, 1), scale = 2^(e+1)
 // if f <= 126/128 and 2^(e+2) otherwise, so that |x| / scale <= 126/256 and the top digit is at most 126 + 1 (carry): int8 holds it.
+// Rows the planes cannot hold (include/nngp_i8s.h): a maximum below 2^-960 counts as zero (scale 1: every digit rounds to 0; 2^(8 ns) / scale
+// would overflow); a NaN, an Inf or an entry >= 1e300 (i8s_mag marks all three as +Inf) gives the scale NaN, which the write-back
+// and every product with this scale inherit -- never a finite wrong value.
 __device__ __forceinline__ double i8s_scale_of(double mx) {
-    if (!(mx > 0.0 && mx < 1.0e300)) return 1.0;
+    if (!(mx < 1.0e300)) return __builtin_nan("");
+    if (!(mx >= 0x1p-960)) return 1.0;
     int e = 0;
     const double f = frexp(mx, &e);
     return ldexp(1.0, f <= 0.984375 ? e + 1 : e + 2);
+}
+
+// |v| for a row maximum: fmax would drop a NaN, so whatever is not below 1e300 becomes +Inf and survives every later fmax
+__device__ __forceinline__ double i8s_mag(double v) {
+    const double a = fabs(v);
+    return a < 1.0e300 ? a : __builtin_inf();
 }
 
 // Symmetric positive semi-definite src (a kernel matrix): |K_ij| <= sqrt(K_ii K_jj), so row i is bounded by sqrt(K_ii max_j K_jj)
@@ -57,7 +67,7 @@ __global__ __launch_bounds__(1024) void k_i8s_diag_bound_scale(const double* __r
                                                                double* __restrict__ scale) {
     __shared__ double red[16];
     double mx = 0.0;
-    for (int64_t i = threadIdx.x; i < n; i += 1024) mx = fmax(mx, fabs(src[i * ld + i]));
+    for (int64_t i = threadIdx.x; i < n; i += 1024) mx = fmax(mx, i8s_mag(src[i * ld + i]));
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off));
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
@@ -91,9 +101,9 @@ __global__ __launch_bounds__(256) void k_i8s_slice_rows(const double* src, int64
         for (int64_t c = 2 * (int64_t)t; c < cols; c += 512) {
             if (c + 1 < cols) {
                 const f64x2 v = *reinterpret_cast<const f64x2*>(p + c);
-                mx = fmax(mx, fmax(fabs(v[0]), fabs(v[1])));
+                mx = fmax(mx, fmax(i8s_mag(v[0]), i8s_mag(v[1])));
             } else {
-                mx = fmax(mx, fabs(p[c]));
+                mx = fmax(mx, i8s_mag(p[c]));
             }
         }
 #pragma unroll
@@ -606,7 +616,8 @@ __global__ __launch_bounds__(256) void k_i8s_floor_ratio(const double* __restric
         s2 = (red[4] + red[5]) + (red[6] + red[7]);
         const double est = sqrt(s2) * coef * i8s_scale_of(mx) * sqrt(sk2[0]);
         const double v = var[r];
-        const double ratio = v > 0.0 ? est / v : (est > 0.0 ? 1.0e300 : 0.0);
+        double ratio = v > 0.0 ? est / v : (est > 0.0 ? 1.0e300 : 0.0);
+        if (ratio != ratio) ratio = 1.0e300;  // a NaN estimate (a row the planes cannot hold) is no reassurance
         atomicMax(out, (unsigned long long)__double_as_longlong(ratio));
     }
 }
@@ -618,7 +629,8 @@ __global__ __launch_bounds__(256) void k_i8s_floor_ratio_rows(const double* __re
     if (r >= rows) return;
     const double est = sqrt(zstat[2 * r]) * coef * i8s_scale_of(zstat[2 * r + 1]) * sqrt(sk2[0]);
     const double v = var[r];
-    const double ratio = v > 0.0 ? est / v : (est > 0.0 ? 1.0e300 : 0.0);
+    double ratio = v > 0.0 ? est / v : (est > 0.0 ? 1.0e300 : 0.0);
+    if (ratio != ratio) ratio = 1.0e300;
     atomicMax(out, (unsigned long long)__double_as_longlong(ratio));
 }
 
@@ -680,6 +692,9 @@ int launch_i8s_scale_sqsum(const double* scale, int64_t n, double* out, hipStrea
 int launch_i8s_floor_ratio(const double* z, int64_t ld, int64_t rows, int64_t cols, const double* var, const I8Plan& pl, int nsa, int nsb,
                            const double* sk2, unsigned long long* out, hipStream_t s) {
     if (rows <= 0) return 0;
+    // the kernel reads the row in pairs and would drop the last column of an odd count
+    NNGP_REQUIRE(cols % 2 == 0 && ld % 2 == 0 && ((uintptr_t)z & 15) == 0, "i8s_floor_ratio: cols and ld must be even, z 16-byte aligned (cols=%lld)",
+                 (long long)cols);
     // pairs on the first dropped diagonal (+ 2 for the two operands' own truncation at their last plane)
     int cut = -1;
     for (int p = 0; p < pl.npairs; ++p) cut = pl.pa[p] + pl.pb[p] > cut ? pl.pa[p] + pl.pb[p] : cut;

@@ -372,8 +372,9 @@ int nngp_gemm_nt_f64(double* c, int64_t ldc, const double* cin, int64_t ldcin, c
  * one IEEE operation in a fixed order, so the device result is reproduced BIT FOR BIT (tests/test_gpu_parity.py).  O(pairs m n k). */
 static double i8s_row_scale(const double* p, int64_t k) {
     double mx = 0.0;
-    for (int64_t c = 0; c < k; ++c) mx = fmax(mx, fabs(p[c]));
-    if (!(mx > 0.0 && mx < 1.0e300)) return 1.0;
+    for (int64_t c = 0; c < k; ++c) mx = fmax(mx, fabs(p[c]) < 1.0e300 ? fabs(p[c]) : HUGE_VAL);  /* a NaN marks the row as an Inf does */
+    if (!(mx < 1.0e300)) return NAN;   /* a row the planes cannot hold: every product with it is NaN (include/nngp_i8s.h) */
+    if (!(mx >= 0x1p-960)) return 1.0; /* ... or one that counts as zero */
     int e = 0;
     const double f = frexp(mx, &e);
     return ldexp(1.0, f <= 0.984375 ? e + 1 : e + 2);  /* |x| / scale <= 126/256: top digit <= 126 + carry */

@@ -176,6 +176,73 @@ def factor_solve_f64(a, y, mode, want=("l", "w", "zt", "ainv", "alpha", "nrs"), 
     return {k: t.cpu().numpy() for k, t in out.items()}
 
 
+I8S_SENTINEL = 0x5A  # what the plane buffers of i8s_cut_rows / i8s_cut_sym hold before the call
+
+
+def i8s_cut_rows(src, ns, ld=None, ldp=None, scale_in=None, writeback=None):
+    """nngp_i8s_cut_rows on src [rows, cols] with leading dimension ld (NaN in the padding): (rc, scales [rows] -- scale_in
+    when given --, planes [ns, rows, ldp] int8 with the sentinel wherever the call wrote nothing, the ldp bytes behind the last
+    plane (one row too many would land there), the source buffer [rows, ld] after the call, the write-back buffer [rows, ld] or
+    None).  writeback: None, "inplace" or "other" (a second buffer filled with NaN)."""
+    lib = _lib.load()
+    rows, cols = src.shape
+    ld = cols + (cols & 1) if ld is None else ld
+    ldp = -(-cols // 128) * 128 if ldp is None else ldp
+    sd = _padded_f64(src, ld)
+    flat = torch.full((ns * rows * ldp + ldp,), I8S_SENTINEL, dtype=torch.int8, device=dev())
+    sc_in = None if scale_in is None else _lib.to_device_f64(scale_in, dev())
+    sc_out = torch.full((rows,), float("nan"), dtype=torch.float64, device=dev())
+    wb = {None: None, "inplace": sd, "other": torch.full((rows, ld), float("nan"), dtype=torch.float64, device=dev())}[writeback]
+    rc = lib.nngp_i8s_cut_rows(_lib.ptr(sd), ld, rows, cols, ns, _lib.ptr(sc_in), _lib.ptr(sc_out), _lib.ptr(flat), ldp, _lib.ptr(wb),
+                               _lib.stream_ptr())
+    torch.cuda.synchronize()
+    flat = flat.cpu().numpy()
+    return (rc, (sc_out if scale_in is None else sc_in).cpu().numpy(), flat[:ns * rows * ldp].reshape(ns, rows, ldp), flat[ns * rows * ldp:],
+            sd.cpu().numpy(), None if wb is None else wb.cpu().numpy())
+
+
+def i8s_cut_sym(kmat, ns, by_rows, ld=None, ldp=None):
+    """nngp_i8s_cut_sym on kmat [n, n]: (rc, scales [n], planes [ns, n, ldp] int8 over the sentinel, sum of the squared scales)."""
+    lib = _lib.load()
+    n = kmat.shape[0]
+    ld = n if ld is None else ld
+    ldp = n if ldp is None else ldp
+    kd = _padded_f64(kmat, ld)
+    planes = torch.full((ns, n, ldp), I8S_SENTINEL, dtype=torch.int8, device=dev())
+    sc = torch.full((n,), float("nan"), dtype=torch.float64, device=dev())
+    sq = torch.full((1,), float("nan"), dtype=torch.float64, device=dev())
+    rc = lib.nngp_i8s_cut_sym(_lib.ptr(kd), ld, n, ns, _lib.ptr(sc), _lib.ptr(planes), ldp, int(by_rows), _lib.ptr(sq), _lib.stream_ptr())
+    torch.cuda.synchronize()
+    return rc, sc.cpu().numpy(), planes.cpu().numpy(), float(sq.item())
+
+
+def i8s_residual(z, kmat, cin, alpha, beta, gamma, ns_z, ns_k, cut, round_z=False, sym=False, base=None, inplace=False, ld_pad=0):
+    """nngp_i8s_residual: dict(rc, out [mp, n], z [mp, n] after the call, and with base [mp] given the fused outputs out32, var,
+    delta, zstat [mp, 2], floor_rows, floor_z).  inplace: cin's buffer is out.  ld_pad: extra (NaN) columns of every operand."""
+    lib = _lib.load()
+    mp, n = z.shape
+    ld = n + ld_pad
+    zd, kd = _padded_f64(z, ld), _padded_f64(kmat, ld)
+    cd = None if cin is None else _padded_f64(cin, ld)
+    od = cd if inplace else torch.full((mp, ld), float("nan"), dtype=torch.float64, device=dev())
+    f = {}
+    if base is not None:
+        f = {"out32": torch.full((mp, n), float("nan"), dtype=torch.float32, device=dev()), "base": _lib.to_device_f64(base, dev()),
+             "var": torch.full((mp,), float("nan"), dtype=torch.float64, device=dev()),
+             "delta": torch.full((mp,), float("nan"), dtype=torch.float64, device=dev()),
+             "zstat": torch.full((mp, 2), float("nan"), dtype=torch.float64, device=dev()),
+             "floor_rows": torch.full((1,), float("nan"), dtype=torch.float64, device=dev()),
+             "floor_z": torch.full((1,), float("nan"), dtype=torch.float64, device=dev())}
+    rc = lib.nngp_i8s_residual(_lib.ptr(od), ld, _lib.ptr(cd), ld, _lib.ptr(zd), ld, _lib.ptr(kd), ld, mp, n, alpha, beta, gamma, ns_z, ns_k,
+                               cut, int(round_z), int(sym), *[_lib.ptr(f.get(k)) for k in
+                                                              ("out32", "base", "var", "delta", "zstat", "floor_rows", "floor_z")],
+                               _lib.stream_ptr())
+    torch.cuda.synchronize()
+    res = {"rc": rc, "out": od[:, :n].cpu().numpy(), "z": zd[:, :n].cpu().numpy()}
+    res.update({k: t.cpu().numpy() for k, t in f.items() if k != "base"})
+    return res
+
+
 def rel_l2(a, b):
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
     return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))

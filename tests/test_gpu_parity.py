@@ -291,11 +291,13 @@ def test_gemm_sliced_int8_is_the_host_restatement_bit_for_bit():
     lib = c_abi.lib()
     vp = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
     for sa, sb, cut in ((5, 5, 4), (4, 6, 3), (7, 7, 6)):
-        assert lib.nngp_gemm_nt_i8s(vp(host), n, vp(c0), n, vp(a), k, vp(b), k, m, n, k, -1.0, 1.0, sa, sb, cut, None) == 0
-        c = torch.full((m, n), float("nan"), device=G.dev(), dtype=torch.float64)
-        G.gemm_nt_i8s(c, torch.from_numpy(c0).to(G.dev()), torch.from_numpy(a).to(G.dev()), torch.from_numpy(b).to(G.dev()),
-                      -1.0, 1.0, sa, sb, cut)
-        assert np.array_equal(c.cpu().numpy(), host), (sa, sb, cut, np.abs(c.cpu().numpy() - host).max())
+        # 0.7, 1.3: a product and a sum that round (both sides are built without contraction, so v += beta cv is two operations on each)
+        for alpha, beta in ((0.7, 1.3), (-1.0, 1.0)):
+            assert lib.nngp_gemm_nt_i8s(vp(host), n, vp(c0), n, vp(a), k, vp(b), k, m, n, k, alpha, beta, sa, sb, cut, None) == 0
+            c = torch.full((m, n), float("nan"), device=G.dev(), dtype=torch.float64)
+            G.gemm_nt_i8s(c, torch.from_numpy(c0).to(G.dev()), torch.from_numpy(a).to(G.dev()), torch.from_numpy(b).to(G.dev()),
+                          alpha, beta, sa, sb, cut)
+            assert np.array_equal(c.cpu().numpy(), host), (sa, sb, cut, alpha, beta, np.abs(c.cpu().numpy() - host).max())
     ref = c0 - (a.astype(np.longdouble) @ b.astype(np.longdouble).T).astype(np.float64)
     unit = np.abs(a).max(1)[:, None] * np.abs(b).max(1)[None, :]
     assert np.max(np.abs(host - ref) / unit) < 2e-14   # 7 x 7 planes, cut 6: float64 grade proper (what is left is the rounding of c0 - product)
