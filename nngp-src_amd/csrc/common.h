@@ -135,6 +135,19 @@ struct BuildArgs {
     const double* comp; // set by launch_kernel_build itself: the composite ReLU map's table (kernel_build.hip), or NULL
     int no_comp;        // 1: keep the per-layer recursion (an NTK model's NNGP kernel: bit-identical whether it comes from the fit's own build or a build of its own)
 };
+// K(x, x) of all n rows in one symmetric build: the operands, the row range and sym.  The caller adds the outputs, their leading
+// dimensions and no_comp.
+inline BuildArgs symmetric_build_args(const double* x, const double* q, int64_t n, int d) {
+    BuildArgs a{};
+    a.x1 = a.x2 = x;
+    a.q1 = a.q2 = q;
+    a.n1 = a.n2 = n;
+    a.d = d;
+    a.row_begin = 0;
+    a.row_end = n;
+    a.sym = 1;
+    return a;
+}
 int launch_row_sqnorm(const double* x, int64_t n, int d, double* q, hipStream_t s);
 int launch_diag_from_q(const double* q, int64_t n, const ArchDev& arch, double* dn, double* dt, hipStream_t s);
 int launch_kernel_build(const BuildArgs& a, const ArchDev& arch, hipStream_t s);  // arch.groups: the summed kernel

@@ -240,6 +240,10 @@ int tri_join(nngp_model* m, hipStream_t s);
 int tri_fork(nngp_model* m, hipStream_t s);
 bool use_split_solves(const nngp_model* m, int64_t mp);
 bool use_tickets(const nngp_model* m, int64_t mp);
+enum class SolvePath { Recursion128, BlocksF32, BlocksH3, Tickets };
+SolvePath solve_path(const nngp_model* m, int64_t mp);  // which triangular solve runs: the whole decision (key 7, use_split_solves, use_tickets)
+// the float32 L^T (ensure_lt) is the backward operand of these; the split paths read the split copy of L^T (ensure_lt_split)
+inline bool needs_lt32(SolvePath p) { return p == SolvePath::Recursion128 || p == SolvePath::BlocksF32; }
 bool cg_from_the_start(const nngp_model* m, int64_t mp);
 int tickets_reserve(const nngp_model* m);
 int tickets_check(nngp_model* m, bool wait);

@@ -104,14 +104,7 @@ int mll_build_a(nngp_mll* h, const ArchDev& arch, int get, double diag_reg, int 
                 hipStream_t s) {
     GpWorkspace& w = h->w;
     const int64_t n = w.n, np = w.np;
-    BuildArgs b{};
-    b.x1 = b.x2 = x;
-    b.q1 = b.q2 = q;
-    b.n1 = b.n2 = n;
-    b.d = w.d;
-    b.row_begin = 0;
-    b.row_end = n;
-    b.sym = 1;
+    BuildArgs b = symmetric_build_args(x, q, n, w.d);
     if (get == NNGP_GET_NTK) b.ntk64 = w.a;
     else b.nngp64 = w.a;
     b.ld64 = np;

@@ -486,14 +486,7 @@ int nngp_sparse_set_inducing(nngp_sparse* h, const double* u, int64_t m, void* s
     NNGP_HIP_CHECK(hipMemcpyAsync(h->u, u, sizeof(double) * m * h->d, hipMemcpyDeviceToDevice, s));
     NNGP_TRY(launch_row_sqnorm(h->u, m, h->d, h->uq, s));
     NNGP_HIP_CHECK(hipMemsetAsync(h->lu, 0, sizeof(double) * mp * mp, s));
-    BuildArgs b{};
-    b.x1 = b.x2 = h->u;
-    b.q1 = b.q2 = h->uq;
-    b.n1 = b.n2 = m;
-    b.d = h->d;
-    b.row_begin = 0;
-    b.row_end = m;
-    b.sym = 1;
+    BuildArgs b = symmetric_build_args(h->u, h->uq, m, h->d);
     b.nngp64 = h->lu;
     b.ld64 = b.ld32 = mp;
     NNGP_TRY(launch_kernel_build(b, h->arch, s));
@@ -584,14 +577,7 @@ int nngp_sparse_predict(nngp_sparse* h, const double* x_test, int64_t mt, int32_
         if (!full) continue;
         // cov = K_tt - P P^T + sigma2 Q Q^T in the padded scratch, then its symmetric part to the caller's [mt, mt]
         NNGP_HIP_CHECK(hipMemsetAsync(h->fc, 0, sizeof(double) * rp * rp, s));
-        BuildArgs b{};
-        b.x1 = b.x2 = xt;
-        b.q1 = b.q2 = xq;
-        b.n1 = b.n2 = rows;
-        b.d = h->d;
-        b.row_begin = 0;
-        b.row_end = rows;
-        b.sym = 1;
+        BuildArgs b = symmetric_build_args(xt, xq, rows, h->d);
         b.nngp64 = h->fc;
         b.ld64 = b.ld32 = rp;
         NNGP_TRY(launch_kernel_build(b, h->arch, s));

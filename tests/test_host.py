@@ -27,6 +27,9 @@ def test_library_loads_and_exports_every_declared_symbol():
     for name in _lib.ABI_SYMBOLS:
         assert hasattr(lib, name), name
     assert not hasattr(lib, "nngp_debug_set"), "the product library must not export the timing knobs"
+    product = open(_lib.LIB_PATH, "rb").read()  # ... nor read the posterior's scheduling aids from the environment
+    for name in (b"NNGP_TK_GATE", b"NNGP_TK_RESERVE", b"NNGP_TK_CUTSTREAM"):
+        assert name not in product, name
     knobs = _lib.load(knobs=True)
     for name in _lib.ABI_SYMBOLS + ("nngp_debug_set",):
         assert hasattr(knobs, name), name
