@@ -73,6 +73,9 @@ SPARSE_ABI_SYMBOLS = ("nngp_sparse_create", "nngp_sparse_destroy", "nngp_sparse_
 # include/nngp_sparse_evidence.h: the sparse model's evidence and its gradient, on the nngp_sparse handle; GPU library only
 SPARSE_EVIDENCE_ABI_SYMBOLS = ("nngp_sparse_reserve_evidence", "nngp_sparse_set_kernel", "nngp_sparse_evidence",
                                "nngp_sparse_evidence_grad", "nngp_sparse_evidence_terms", "nngp_sparse_adjoint_rect")
+# include/nngp_sparse_ard.h: per-feature relevances on the nngp_sparse handle and the evidence's derivative with respect to them
+SPARSE_ARD_ABI_SYMBOLS = ("nngp_sparse_reserve_ard", "nngp_sparse_set_relevance", "nngp_sparse_evidence_grad_ard",
+                          "nngp_sparse_ard_terms", "nngp_sparse_ard_rect")
 # include/nngp_i8s.h: the stand-alone operators of the sliced int8 product (cuts, residual, fused statistics); GPU library only
 I8S_ABI_SYMBOLS = ("nngp_i8s_cut_rows", "nngp_i8s_cut_sym", "nngp_i8s_residual")
 BOUND_DTC, BOUND_VFE = 0, 1
@@ -142,6 +145,7 @@ def load(knobs: bool = False):
     bind_pool_prototypes(lib)
     bind_sparse_prototypes(lib)
     bind_sparse_evidence_prototypes(lib)
+    bind_sparse_ard_prototypes(lib)
     bind_i8s_prototypes(lib)
     _libs[knobs] = lib
     return lib
@@ -348,6 +352,20 @@ def bind_sparse_evidence_prototypes(lib):
     lib.nngp_sparse_evidence_terms.argtypes = [vp, pd, i32]
     lib.nngp_sparse_adjoint_rect.argtypes = [vp, i64, vp, i64, i32, archp, vp, i64, vp, vp, pd, vp]
     for name in SPARSE_EVIDENCE_ABI_SYMBOLS:
+        getattr(lib, name).restype = ctypes.c_int
+    return lib
+
+
+def bind_sparse_ard_prototypes(lib):
+    """Argument and result types of include/nngp_sparse_ard.h (the HIP library only)."""
+    vp, i64, i32, dbl = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_double
+    pd, archp = ctypes.POINTER(dbl), ctypes.POINTER(NngpArchAct)
+    lib.nngp_sparse_reserve_ard.argtypes = [vp]
+    lib.nngp_sparse_set_relevance.argtypes = [vp, pd]
+    lib.nngp_sparse_evidence_grad_ard.argtypes = [vp, vp, vp, i64, i32, pd, pd, pd, vp]
+    lib.nngp_sparse_ard_terms.argtypes = [vp, pd, i32]
+    lib.nngp_sparse_ard_rect.argtypes = [vp, i64, vp, i64, i32, archp, pd, vp, i64, vp, vp, pd, vp]
+    for name in SPARSE_ARD_ABI_SYMBOLS:
         getattr(lib, name).restype = ctypes.c_int
     return lib
 

@@ -8,7 +8,7 @@
 //                   and products on the float64 MFMA GEMM); then the symmetric adjoint pass of nngp_adjoint.h over K_uu
 //                   (adjoint_tile<NLC, false, false>: alpha := gamma, the matrix seed := E with the jitter's share on its diagonal)
 //   per chunk       the cross build K_cu (no solve), beta_c = (y_c - K_cu gamma) / sigma2, D_c = K_cu M' on the MFMA GEMM, and
-//   k_sparse_rect_partial   the new kernel: the adjoint of the layer recursion over the rectangular block K(X_c, U).  One workgroup
+//   k_sparse_rect_partial   (sparse_rect.h) the adjoint of the layer recursion over the rectangular block K(X_c, U).  One workgroup
 //                   per 64 x 64 tile of (rows of X_c) x (rows of U); it mirrors adjoint_tile -- the q chains of the tile's rows
 //                   and columns in the kernel build's order of operations, the Gram tile from LDS-staged feature chunks, per entry
 //                   the forward recursion (ReLU and ABRelu, the q = 0 rule, pi_minus_atan2 on kTrigTab) and the reverse sweep --
@@ -19,177 +19,13 @@
 //   k_ev_reduce     one workgroup sums the slots in ascending order and adds the chunk's sums to the accumulators.
 // No float atomics, no device-side counter, no workgroup waits for another: a launch boundary is the only synchronisation, so
 // nothing here can hang and two runs give the same bits.
-#include "nngp_adjoint.h"
+#include "sparse_rect.h"
 #include "sparse_gp.h"
 #include "../../include/nngp_sparse_evidence.h"
 
 namespace nngp {
 
 namespace {
-
-struct RectArgs {
-    const double* x;      // [c, d]
-    const double* xq;     // [c]: |x_i|^2 / d
-    int64_t c;
-    const double* u;      // [m, d]
-    const double* uq;     // [m]
-    int64_t m;
-    int d;
-    const double* seed;   // [c, ld]: D
-    int64_t ld;
-    const double* beta;   // [c]
-    const double* gamma;  // [m]
-    double* part;         // [2 ncomp][nparts]: the beta gamma^T half of every component, then the D half
-    int64_t nparts;       // tiles: ceil(c / 64) * tu
-    int64_t tu;           // tiles along the inducing rows
-};
-
-template <int NLC>
-__device__ __forceinline__ void rect_tile(const RectArgs& a, const ArchDev& arch) {
-    __shared__ __attribute__((aligned(16))) double sm[2 * MT * MLD];  // the two row panels, then the Gram tile [MT][MT + 1]
-    __shared__ double qs[NLC][2 * MT];  // rows | columns: q at the input of Dense layer l
-    __shared__ double rq[NLC][2 * MT];  // 1 / (4 pi q') with q' after Dense layer l; 0 where q' = 0 (the q = 0 rule)
-    __shared__ __attribute__((aligned(16))) double tab[65 * 4];
-    __shared__ double red[256];
-    static_assert(MT * (MT + 1) <= 2 * MT * MLD, "the Gram tile aliases the panels");
-    const int tid = threadIdx.x, tc = tid & 15, tr = tid >> 4;
-    const int nd = arch.n_dense;
-    const int64_t t = xcd_tile(blockIdx.x, a.nparts);
-    const int64_t i0 = (t / a.tu) * MT, j0 = (t % a.tu) * MT;
-    for (int e = tid; e < 65 * 4; e += 256) tab[e] = kTrigTab[e >> 2][e & 3];
-    if (tid < 2 * MT) {  // the q chain of the tile's rows and columns, in the kernel build's order of operations
-        double q;
-        if (tid < MT) q = i0 + tid < a.c ? a.xq[i0 + tid] : 0.0;
-        else q = j0 + tid - MT < a.m ? a.uq[j0 + tid - MT] : 0.0;
-#pragma unroll
-        for (int l = 0; l < NLC; ++l) {
-            if (l < nd) {
-                qs[l][tid] = q;
-                const double qp = fma(arch.w2[l], q, arch.b2[l]);
-                rq[l][tid] = qp > 0.0 ? 1.0 / (4.0 * kPi * qp) : 0.0;
-                if (l < nd - 1) q = arch.act[l] == NNGP_ACT_ABRELU ? arch.ap[l][2] * qp : 0.5 * qp;
-            }
-        }
-    }
-
-    // ---- Gram tile: rows i0 + tr + 16 p of X_c, columns j0 + tc + 16 q of U, features summed in order ----
-    double (*s1)[MLD] = reinterpret_cast<double (*)[MLD]>(sm);
-    double (*s2)[MLD] = reinterpret_cast<double (*)[MLD]>(sm + MT * MLD);
-    double acc[4][4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc[p][q] = 0.0;
-    for (int k0 = 0; k0 < a.d; k0 += MKC) {
-        const int kc = a.d - k0 < MKC ? a.d - k0 : MKC;
-        for (int e = tid; e < MT * MKC; e += 256) {
-            const int r = e / MKC, k = e % MKC;
-            const int64_t i = i0 + r, j = j0 + r;
-            s1[r][k] = (k < kc && i < a.c) ? a.x[i * a.d + k0 + k] : 0.0;
-            s2[r][k] = (k < kc && j < a.m) ? a.u[j * a.d + k0 + k] : 0.0;
-        }
-        __syncthreads();
-        for (int k = 0; k < kc; ++k) {
-            double uu[4], vv[4];
-#pragma unroll
-            for (int p = 0; p < 4; ++p) uu[p] = s1[tr + 16 * p][k];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) vv[q] = s2[tc + 16 * q][k];
-#pragma unroll
-            for (int p = 0; p < 4; ++p)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[p][q] = fma(uu[p], vv[q], acc[p][q]);
-        }
-        __syncthreads();
-    }
-    double (*gt)[MT + 1] = reinterpret_cast<double (*)[MT + 1]>(sm);
-    const double inv_d = 1.0 / (double)a.d;
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) gt[tr + 16 * p][tc + 16 * q] = acc[p][q] * inv_d;
-    __syncthreads();
-
-    // ---- per entry: forward recursion, then the adjoint sweep from both seeds ----
-    double ga[2 * NLC], gi[2 * NLC];
-#pragma unroll
-    for (int c = 0; c < 2 * NLC; ++c) ga[c] = gi[c] = 0.0;
-#pragma unroll 1
-    for (int e = 0; e < 16; ++e) {
-        const int ri = tr + 16 * (e >> 2), cj = tc + 16 * (e & 3);
-        const int64_t i = i0 + ri, j = j0 + cj;
-        if (i >= a.c || j >= a.m) continue;  // the tile's tails
-        double kb_a = a.beta[i] * a.gamma[j];
-        double kb_i = a.seed[i * a.ld + j];
-        double k = gt[ri][cj];
-        double kin[NLC], ck[NLC], cs[NLC];  // per layer: k into Dense l; dK'/dk and (b - a)^2 s of the activation after it
-#pragma unroll
-        for (int l = 0; l < NLC; ++l) {
-            kin[l] = k;
-            ck[l] = 0.0;
-            cs[l] = 0.0;
-            if (l < nd - 1) {
-                const double v = arch.w2[l], c = arch.b2[l];
-                const bool ab = arch.act[l] == NNGP_ACT_ABRELU;
-                k = fma(v, k, c);
-                const double q1 = fma(v, qs[l][ri], c), q2 = fma(v, qs[l][MT + cj], c);
-                const double rr = fma(q1, q2, -k * k);
-                const double s = rr > 0.0 ? fast_sqrt_pos(rr > 0.0 ? rr : 1.0) : 0.0;
-                const double kr = pi_minus_atan2(s, k, tab) * (0.5 / kPi);  // kdot
-                const double kk = fma(kr, k, s * (0.5 / kPi));
-                if (ab) {
-                    k = fma(arch.ap[l][0], k, arch.ap[l][1] * kk);
-                    ck[l] = fma(arch.ap[l][1], kr, arch.ap[l][0]);
-                    cs[l] = arch.ap[l][1] * s;
-                } else {
-                    k = kk;
-                    ck[l] = kr;
-                    cs[l] = s;
-                }
-            }
-        }
-        double q1a = 0.0, q2a = 0.0, q1i = 0.0, q2i = 0.0;
-#pragma unroll
-        for (int l = NLC - 1; l >= 0; --l) {
-            if (l < nd) {
-                if (l < nd - 1) {  // the activation after Dense layer l: dK'/dq1 = (b - a)^2 s / (4 pi q1'), q' = h q
-                    const double h = arch.act[l] == NNGP_ACT_ABRELU ? arch.ap[l][2] : 0.5;
-                    const double t1 = cs[l] * rq[l][ri], t2 = cs[l] * rq[l][MT + cj];
-                    q1a = fma(kb_a, t1, h * q1a);
-                    q2a = fma(kb_a, t2, h * q2a);
-                    kb_a *= ck[l];
-                    q1i = fma(kb_i, t1, h * q1i);
-                    q2i = fma(kb_i, t2, h * q2i);
-                    kb_i *= ck[l];
-                }
-                // Dense layer l: k' = v k + c (likewise q1, q2)
-                const double v = arch.w2[l], x1 = qs[l][ri], x2 = qs[l][MT + cj];
-                ga[2 * l] += fma(kb_a, kin[l], fma(q1a, x1, q2a * x2));
-                ga[2 * l + 1] += kb_a + q1a + q2a;
-                gi[2 * l] += fma(kb_i, kin[l], fma(q1i, x1, q2i * x2));
-                gi[2 * l + 1] += kb_i + q1i + q2i;
-                kb_a *= v;
-                q1a *= v;
-                q2a *= v;
-                kb_i *= v;
-                q1i *= v;
-                q2i *= v;
-            }
-        }
-    }
-    const int ncomp = 2 * nd;
-#pragma unroll
-    for (int c = 0; c < 2 * NLC; ++c) {
-        if (c < ncomp) {  // uniform over the workgroup
-            const double ra = block_sum(ga[c], red);
-            const double rb = block_sum(gi[c], red);
-            if (tid == 0) {
-                a.part[(int64_t)c * a.nparts + blockIdx.x] = ra;
-                a.part[(int64_t)(ncomp + c) * a.nparts + blockIdx.x] = rb;
-            }
-        }
-    }
-}
 
 template <int NLC>
 __global__ __launch_bounds__(256) void k_sparse_rect_partial(RectArgs a, ArchDev arch) {
@@ -369,6 +205,7 @@ int sparse_evidence_sums(nngp_sparse* h, const double* xq, const double* y, int6
 void sparse_evidence_free(nngp_sparse* h) {
     for (double** p : {&h->ev_a, &h->ev_m, &h->ev_t, &h->ev_d, &h->ev_vec, &h->ev_part}) dev_free(*p);
     h->ev_reserved = false;
+    sparse_ard_free(h);
 }
 
 }  // namespace nngp
@@ -427,12 +264,21 @@ int nngp_sparse_evidence(nngp_sparse* h, int32_t bound, double* nlml, void* stre
 
 int nngp_sparse_evidence_grad(nngp_sparse* h, const double* x, const double* y, int64_t n, int32_t bound, double* nlml, double* grad,
                               void* stream) {
-    hipStream_t s = (hipStream_t)stream;
     NNGP_REQUIRE(h != nullptr && x != nullptr && y != nullptr && nlml != nullptr && grad != nullptr, "sparse_evidence_grad: NULL argument");
-    NNGP_TRY(evidence_check(h, bound, "sparse_evidence_grad"));
-    NNGP_REQUIRE(h->ev_reserved, "sparse_evidence_grad: the evidence was not reserved (nngp_sparse_reserve_evidence)");
-    NNGP_REQUIRE(n == h->n, "sparse_evidence_grad: n=%lld, but %lld rows were added", (long long)n, (long long)h->n);
+    return sparse_evidence_grad_core(h, x, y, n, bound, nlml, grad, nullptr, "sparse_evidence_grad", (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+int nngp::sparse_evidence_grad_core(nngp_sparse* h, const double* x, const double* y, int64_t n, int bound, double* nlml, double* grad,
+                                    double* grad_s, const char* who, hipStream_t s) {
+    NNGP_TRY(evidence_check(h, bound, who));
+    NNGP_REQUIRE(h->ev_reserved, "%s: the evidence was not reserved (nngp_sparse_reserve_evidence)", who);
+    NNGP_REQUIRE(n == h->n, "%s: n=%lld, but %lld rows were added", who, (long long)n, (long long)h->n);
+    const bool ard = grad_s != nullptr;
+    NNGP_REQUIRE(!ard || h->have_rel, "%s: no relevances on the handle (nngp_sparse_set_relevance)", who);
     h->have_terms = false;
+    h->have_ard_terms = false;
     const bool vfe = bound == NNGP_BOUND_VFE;
     const int64_t m = h->m, mp = h->mp;
     const int nd = h->arch.n_dense, ncomp = 2 * nd;
@@ -483,8 +329,13 @@ int nngp_sparse_evidence_grad(nngp_sparse* h, const double* x, const double* y, 
     NNGP_HIP_CHECK(hipGetLastError());
     {
         const int64_t tiles = gp_lower_tiles(m);
-        MllArgs ma{h->u, h->uq, m, h->d, M, mp, gamma, nullptr, h->ev_part, tiles};
-        NNGP_TRY(launch_uu(ma, h->arch, s));
+        if (ard) {  // T = W is dead from here on: the seeded adjoints of K0 over K_uu go there
+            NNGP_TRY(sparse_ard_begin(h, s));
+            NNGP_TRY(sparse_ard_uu(h, M, gamma, T, s));
+        } else {
+            MllArgs ma{h->u, h->uq, m, h->d, M, mp, gamma, nullptr, h->ev_part, tiles};
+            NNGP_TRY(launch_uu(ma, h->arch, s));
+        }
         NNGP_TRY(reduce_into(h->ev_part, tiles, 2 * ncomp, h->scal + kSpAccUu, s));
     }
 
@@ -492,17 +343,28 @@ int nngp_sparse_evidence_grad(nngp_sparse* h, const double* x, const double* y, 
     const int64_t tu = (m + MT - 1) / MT;
     for (int64_t r0 = 0; r0 < n; r0 += h->chunk_rows) {
         const int64_t c = (n - r0 < h->chunk_rows) ? n - r0 : h->chunk_rows, rp = round_up(c, TB);
-        const double* xc = x + r0 * h->d;
+        const double* xraw = x + r0 * h->d;
+        const double* xc = xraw;
+        if (h->have_rel) {
+            NNGP_TRY(sparse_ard_scale(h, xraw, c, h->ard_xs, s));
+            xc = h->ard_xs;
+        }
         NNGP_TRY(launch_row_sqnorm(xc, c, h->d, h->xq, s));
         NNGP_TRY(sparse_cross(h, xc, h->xq, c, h->chunk, s, 2));  // K_cu, no solve
         hipLaunchKernelGGL(k_ev_beta, dim3((unsigned)c), dim3(256), 0, s, h->chunk, mp, m, gamma, y + r0, s2, beta);
         hipLaunchKernelGGL(k_ev_sumsq, dim3(1), dim3(256), 0, s, beta, c, h->scal + kSpSums + 4);
         NNGP_HIP_CHECK(hipGetLastError());
         NNGP_TRY(launch_gemm_nt_f64(h->ev_d, mp, nullptr, 0, h->chunk, mp, A, mp, rp, mp, mp, 1.0, 0.0, s));  // D_c = K_cu M'
-        RectArgs ra{xc, h->xq, c, h->u, h->uq, m, h->d, h->ev_d, mp, beta, gamma, h->ev_part, ((c + MT - 1) / MT) * tu, tu};
-        NNGP_TRY(launch_rect(ra, h->arch, s));
-        NNGP_TRY(reduce_into(h->ev_part, ra.nparts, 2 * ncomp, h->scal + kSpAccFu, s));
+        const int64_t nparts = ((c + MT - 1) / MT) * tu;
+        if (ard) {
+            NNGP_TRY(sparse_ard_chunk(h, xraw, xc, c, beta, gamma, s));
+        } else {
+            RectArgs ra{xc, h->xq, c, h->u, h->uq, m, h->d, h->ev_d, mp, beta, gamma, h->ev_part, nparts, tu};
+            NNGP_TRY(launch_rect(ra, h->arch, s));
+        }
+        NNGP_TRY(reduce_into(h->ev_part, nparts, 2 * ncomp, h->scal + kSpAccFu, s));
     }
+    if (ard) NNGP_TRY(sparse_ard_end(h, s));
 
     // ---- the fixed-order finish on the host ----
     double sc[kSpScal];
@@ -533,8 +395,9 @@ int nngp_sparse_evidence_grad(nngp_sparse* h, const double* x, const double* y, 
         }
         t[2 * p] = qa;
         t[2 * p + 1] = ta;
-        grad[p] = -0.5 * qa + 0.5 * ta;
+        if (grad != nullptr) grad[p] = -0.5 * qa + 0.5 * ta;
     }
+    if (ard) sparse_ard_finish_host(h, vfe, s2, ts, bb, gg, grad_s);
     double* tail = t + 2 * (ncomp + 1);
     tail[0] = sc[kSpSums];
     tail[1] = sc[kSpYY] - sc[kSpSums + 1];
@@ -547,6 +410,8 @@ int nngp_sparse_evidence_grad(nngp_sparse* h, const double* x, const double* y, 
     h->have_terms = true;
     return 0;
 }
+
+extern "C" {
 
 int nngp_sparse_evidence_terms(const nngp_sparse* h, double* out, int32_t count) {
     NNGP_REQUIRE(h != nullptr && out != nullptr, "sparse_evidence_terms: NULL argument");

@@ -3,6 +3,8 @@
 #pragma once
 #include "gp_f64.h"
 
+#include <vector>
+
 // slots of nngp_sparse::scal.  [0, 4) are the fit's own; the rest belongs to the evidence (include/nngp_sparse_evidence.h)
 constexpr int kSpYY = 4;           // y^T y of the rows added
 constexpr int kSpQ = 8;            // [NNGP_MAX_DENSE] sum_i q_i^(l) of the rows added: tr dK_ff / dtheta in closed form
@@ -63,6 +65,23 @@ struct nngp_sparse {
     bool have_terms = false;
     int n_terms = 0;
     double terms[2 * (2 * NNGP_MAX_DENSE + 1) + 7] = {};
+    // per-feature relevances (nngp_sparse_reserve_ard, include/nngp_sparse_ard.h); all NULL / empty on a handle that never reserves
+    bool ard_reserved = false;
+    bool have_rel = false;       // nngp_sparse_set_relevance gave relevances: every entry point takes raw rows and scales them
+    double* ard_s = nullptr;     // [2 d]: s, then sqrt(s) (taken on the host)
+    double* ard_u = nullptr;     // [m_cap, d] the raw inducing rows (u holds them scaled)
+    double* ard_xs = nullptr;    // [max(chunk_rows, test_cap), d] a chunk or a test block, scaled
+    double* ard_fxs = nullptr;   // [ard_fcap, d] the test rows of a full-covariance predict, scaled (grown with fp / fq)
+    int64_t ard_fcap = 0;
+    double* ard_kb = nullptr;    // [chunk_rows, mp_cap] kbar of the rank-one seed (kbar of the dense seed overwrites ev_d)
+    double* ard_qrow = nullptr;  // [2][column tiles][chunk_rows] RectArgs::qrow
+    double* ard_qcol = nullptr;  // [2][row tiles of a chunk][mp_cap] RectArgs::qcol
+    double* ard_qbar = nullptr;  // [2][tiles per side][mp_cap] MllArgs::qbar of the pass over K_uu
+    double* ard_part = nullptr;  // [3][row blocks][d] per row block the contraction of either seed and sum x_ik^2 (a chunk, or U)
+    double* ard_acc = nullptr;   // [8 d + 2 mp_cap]: the chunks' sums [3 d], the column terms [2 d], the K_uu half [3 d], then
+                                 // per seed sum_i qbar2 over every row of every chunk [2][mp_cap]
+    std::vector<double> ard_host, ard_terms;  // ard_acc's first 8 d on the host; nngp_sparse_ard_terms (4 d)
+    bool have_ard_terms = false;
 };
 
 namespace nngp {
@@ -73,4 +92,23 @@ int sparse_cross(nngp_sparse* h, const double* x, const double* xq, int64_t rows
 // fixed order
 int sparse_evidence_sums(nngp_sparse* h, const double* xq, const double* y, int64_t c, hipStream_t s);
 void sparse_evidence_free(nngp_sparse* h);
+// The evaluation behind nngp_sparse_evidence_grad and nngp_sparse_evidence_grad_ard.  grad_s: host, d values, or NULL for the
+// pass without relevances' derivatives; x holds raw rows when the handle has relevances.
+int sparse_evidence_grad_core(nngp_sparse* h, const double* x, const double* y, int64_t n, int bound, double* nlml, double* grad,
+                              double* grad_s, const char* who, hipStream_t s);
+// sparse_ard.hip (include/nngp_sparse_ard.h).  sparse_ard_scale: out [rows, d] = x o sqrt(s), one multiply per element.
+// The gradient's steps, in call order: begin zeroes the accumulators; uu runs the symmetric pass over K_uu with ARD set (the
+// layer partials land in ev_part as from the plain pass; cmat: an [mp, mp] scratch) and its contraction with the raw inducing
+// rows; chunk runs the rectangular pass with ARD set over one chunk (layer partials in ev_part likewise; xs the scaled rows,
+// x_raw the raw ones; ev_d holds D_c and is overwritten) and the contraction; end adds the column terms and queues the host copy;
+// finish_host (after the stream is synchronised) assembles grad_s and the terms.
+int sparse_ard_scale(const nngp_sparse* h, const double* x, int64_t rows, double* out, hipStream_t s);
+int sparse_ard_begin(nngp_sparse* h, hipStream_t s);
+int sparse_ard_uu(nngp_sparse* h, const double* seed, const double* gamma, double* cmat, hipStream_t s);
+int sparse_ard_chunk(nngp_sparse* h, const double* x_raw, const double* xs, int64_t c, const double* beta, const double* gamma,
+                     hipStream_t s);
+int sparse_ard_end(nngp_sparse* h, hipStream_t s);
+void sparse_ard_finish_host(nngp_sparse* h, bool vfe, double s2, double ts, double bb, double gg, double* grad_s);
+int sparse_ard_full_reserve(nngp_sparse* h, int64_t cap, hipStream_t s);  // grows ard_fxs to cap rows
+void sparse_ard_free(nngp_sparse* h);
 }  // namespace nngp

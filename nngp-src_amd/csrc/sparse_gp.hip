@@ -483,7 +483,12 @@ int nngp_sparse_set_inducing(nngp_sparse* h, const double* u, int64_t m, void* s
     h->finished = false;
     h->sigma2 = 0.0;
     const int64_t mp = round_up(m, TB);
-    NNGP_HIP_CHECK(hipMemcpyAsync(h->u, u, sizeof(double) * m * h->d, hipMemcpyDeviceToDevice, s));
+    if (h->have_rel) {  // u holds raw rows: kept for the relevance gradient, scaled for everything else
+        NNGP_HIP_CHECK(hipMemcpyAsync(h->ard_u, u, sizeof(double) * m * h->d, hipMemcpyDeviceToDevice, s));
+        NNGP_TRY(sparse_ard_scale(h, h->ard_u, m, h->u, s));
+    } else {
+        NNGP_HIP_CHECK(hipMemcpyAsync(h->u, u, sizeof(double) * m * h->d, hipMemcpyDeviceToDevice, s));
+    }
     NNGP_TRY(launch_row_sqnorm(h->u, m, h->d, h->uq, s));
     NNGP_HIP_CHECK(hipMemsetAsync(h->lu, 0, sizeof(double) * mp * mp, s));
     BuildArgs b = symmetric_build_args(h->u, h->uq, m, h->d);
@@ -511,6 +516,10 @@ int nngp_sparse_add_rows(nngp_sparse* h, const double* x, const double* y, int64
     for (int64_t r0 = 0; r0 < n; r0 += h->chunk_rows) {
         const int64_t c = (n - r0 < h->chunk_rows) ? n - r0 : h->chunk_rows;
         const double* xc = x + r0 * h->d;
+        if (h->have_rel) {
+            NNGP_TRY(sparse_ard_scale(h, xc, c, h->ard_xs, s));
+            xc = h->ard_xs;
+        }
         NNGP_TRY(launch_row_sqnorm(xc, c, h->d, h->xq, s));
         NNGP_TRY(launch_kernel_diag(xc, h->xq, c, h->d, h->arch, h->kd, nullptr, s));
         hipLaunchKernelGGL(k_sparse_trace, dim3(1), dim3(256), 0, s, h->kd, c, h->scal);
@@ -559,10 +568,16 @@ int nngp_sparse_predict(nngp_sparse* h, const double* x_test, int64_t mt, int32_
     const int64_t mp = h->mp;
     const bool full = cov_mode == NNGP_COV_FULL;
     if (full) NNGP_TRY(sparse_full_reserve(h, mt, s));
+    if (full && h->have_rel) NNGP_TRY(sparse_ard_full_reserve(h, round_up(mt, TB), s));
     const int64_t blk = full ? mt : h->test_cap;
     for (int64_t r0 = 0; r0 < mt; r0 += blk) {
         const int64_t rows = (mt - r0 < blk) ? mt - r0 : blk, rp = round_up(rows, TB);
         const double* xt = x_test + r0 * h->d;
+        if (h->have_rel) {
+            double* xs = full ? h->ard_fxs : h->ard_xs;
+            NNGP_TRY(sparse_ard_scale(h, xt, rows, xs, s));
+            xt = xs;
+        }
         double* pm = full ? h->fp : h->pt;
         double* qm = full ? h->fq : h->qt;
         double* xq = full ? h->fxq : h->xq;

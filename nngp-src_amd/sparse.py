@@ -7,6 +7,10 @@ conditional variance of the prior kernel (``nngp_pool_select_greedy``), or at ra
 
 The model's evidence and its gradient (``include/nngp_sparse_evidence.h``) tune W_std / b_std / diag_reg at the N the sparse model
 is for: ``SparseGPModel.evidence`` / ``evidence_grad``, the evaluator ``SparseEvidence`` and ``tune_hyperparameters``.
+
+Per-feature relevances (ARD, ``include/nngp_sparse_ard.h``): ``SparseGPModel.reserve_evidence_ard`` / ``set_relevance`` put one
+s_k >= 0 per input feature on the handle, K(x o sqrt(s), x' o sqrt(s)), and ``evidence_grad(..., ard=True)`` also returns the
+evidence's derivative with respect to every s_k, at the same O(N m^2); ``tune_hyperparameters(ard=True)`` tunes them.
 """
 from __future__ import annotations
 
@@ -54,6 +58,7 @@ class SparseGPModel(HasSpec):
         self._check(self.spec.sparse_create(self.lib, ctypes.byref(self.handle), self.m_cap, self.chunk_rows, int(test_cap), self.d,
                                             self.ny, float(diag_reg), int(bool(diag_reg_absolute_scale)), float(jitter)))
         self.m = 0
+        self.relevance = None  # set_relevance: the handle then scales the raw rows itself
 
     @classmethod
     def from_kernel_fn(cls, kernel_fn, m_cap: int, d: int, **kwargs):
@@ -173,9 +178,44 @@ class SparseGPModel(HasSpec):
         self._check(self.lib.nngp_sparse_evidence(self.handle, bound_code(bound), ctypes.byref(nlml), _lib.stream_ptr()))
         return nlml.value
 
-    def evidence_grad(self, x, y, bound="vfe"):
+    # ---- per-feature relevances (include/nngp_sparse_ard.h) ----
+    def reserve_evidence_ard(self):
+        """reserve_evidence plus what the relevances and their gradient need (nngp_sparse_reserve_ard); repeatable."""
+        self.reserve_evidence()
+        self._check(self.lib.nngp_sparse_reserve_ard(self.handle))
+        return self
+
+    def set_relevance(self, s):
+        """One relevance s_k >= 0 per input feature (None: none again): K(x o sqrt(s), x' o sqrt(s)).  Forgets the inducing rows
+        and the training rows; from then on every method takes raw rows and the handle scales them.  A model whose spec carries
+        an input_scale refuses: one mechanism or the other."""
+        if self.spec.input_scale is not None:
+            raise ValueError("set_relevance on a model with an input_scale: use one mechanism or the other")
+        if s is None:
+            self._check(self.lib.nngp_sparse_set_relevance(self.handle, None))
+            self.relevance = None
+        else:
+            s = np.ascontiguousarray(s, dtype=np.float64).reshape(-1)
+            if s.shape[0] != self.d:
+                raise ValueError("relevances need one value per feature (%d), got %d" % (self.d, s.shape[0]))
+            self._check(self.lib.nngp_sparse_set_relevance(self.handle, s.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+            self.relevance = s.copy()
+        self.m = 0
+        return self
+
+    def evidence_ard_terms(self):
+        """Of the last evidence_grad(ard=True) (nngp_sparse_ard_terms): ``quad[k]``, ``trace[k]`` with grad_s = -quad / 2 + trace / 2
+        per feature, ``tr_dkff`` = tr dK_ff/ds_k and ``tr_dkuu`` = tr dK_uu/ds_k."""
+        d = self.d
+        out = (ctypes.c_double * (4 * d))()
+        self._check(self.lib.nngp_sparse_ard_terms(self.handle, out, 4 * d))
+        v = np.array(out[:], dtype=np.float64)
+        return {"quad": v[0:2 * d:2], "trace": v[1:2 * d:2], "tr_dkff": v[2 * d:3 * d], "tr_dkuu": v[3 * d:4 * d]}
+
+    def evidence_grad(self, x, y, bound="vfe", ard=False):
         """(nlml, grad): x, y are the rows that were added, handed again.  grad (numpy, 2 n_dense + 1 values): d/dsigma_w,l^2,
-        d/dsigma_b,l^2 for every Dense layer l, then d/dlambda, with the inducing rows held fixed."""
+        d/dsigma_b,l^2 for every Dense layer l, then d/dlambda, with the inducing rows held fixed.  ``ard``: (nlml, grad, grad_s)
+        with grad_s (d values) the derivatives with respect to the relevances of set_relevance."""
         code = bound_code(bound)
         xd = _lib.to_device_f64(x, self.device)
         n = self._rows(xd, "x")
@@ -185,6 +225,11 @@ class SparseGPModel(HasSpec):
             raise ValueError("y must have one value per row of x (%d), got %s" % (n, tuple(yd.shape)))
         nlml = ctypes.c_double()
         g = (ctypes.c_double * (2 * self.spec.n_dense + 1))()
+        if ard:
+            gs = (ctypes.c_double * self.d)()
+            self._check(self.lib.nngp_sparse_evidence_grad_ard(self.handle, _lib.ptr(xd), _lib.ptr(yd), n, code, ctypes.byref(nlml), g,
+                                                               gs, _lib.stream_ptr()))  # synchronises: xd, yd may go
+            return nlml.value, np.array(g[:], dtype=np.float64), np.array(gs[:], dtype=np.float64)
         self._check(self.lib.nngp_sparse_evidence_grad(self.handle, _lib.ptr(xd), _lib.ptr(yd), n, code, ctypes.byref(nlml), g,
                                                        _lib.stream_ptr()))  # synchronises: xd, yd may go
         return nlml.value, np.array(g[:], dtype=np.float64)
@@ -300,8 +345,11 @@ class SparseEvidence:
     set_kernel -> set_inducing -> add_rows -> finish -> evidence[_grad] on one handle, with the rows kept on the device.
     ``inducing``: the rows themselves [m, d], or indices into x."""
 
-    def __init__(self, x, y, inducing, bound="vfe", chunk_rows: int = 8192, jitter: float = 1e-8):
+    def __init__(self, x, y, inducing, bound="vfe", chunk_rows: int = 8192, jitter: float = 1e-8, ard: bool = False):
+        """``ard``: ``evaluate`` also takes ``relevance=`` (d values) and returns ``(value, grad, grad_s)``, the shape
+        ``mll.tune_loop`` expects from an evaluator with relevances; x and the inducing rows are the raw rows."""
         bound_code(bound)
+        self.ard = bool(ard)
         x = np.ascontiguousarray(x, dtype=np.float64)
         inducing = np.asarray(inducing)
         if inducing.ndim == 1:
@@ -315,17 +363,32 @@ class SparseEvidence:
         self.chunk_rows = min(int(chunk_rows), -(-int(self.x.shape[0]) // 128) * 128)
         self.model = None
 
-    def evaluate(self, params, diag_reg=1e-3, absolute=False, with_grad=True):
-        """(nlml, grad) at ``params`` = a kernel_fn or (w_std, b_std, activations); grad is None without ``with_grad``."""
+    def evaluate(self, params, diag_reg=1e-3, absolute=False, with_grad=True, relevance=None):
+        """(nlml, grad) at ``params`` = a kernel_fn or (w_std, b_std, activations); grad is None without ``with_grad``.  With
+        ``relevance`` (an evaluator made with ``ard=True``): (nlml, grad, grad_s) at these relevances."""
         spec = check_evidence_spec(KernelSpec.of(params))
+        if relevance is not None and not self.ard:
+            raise ValueError("relevance= needs SparseEvidence(..., ard=True)")
         if self.model is None:
             self.model = SparseGPModel(int(self.u.shape[0]), int(self.x.shape[1]), diag_reg=diag_reg, chunk_rows=self.chunk_rows,
                                        jitter=self.jitter, test_cap=128, diag_reg_absolute_scale=absolute,
                                        **spec.as_keywords()).reserve_evidence()
-        self.model.set_kernel(spec, diag_reg, absolute).set_inducing(self.u).add_rows(self.x, self.y).finish()
+            if self.ard:
+                self.model.reserve_evidence_ard()
+        self.model.set_kernel(spec, diag_reg, absolute)
+        if self.ard:
+            self.model.set_relevance(relevance)
+        self.model.set_inducing(self.u).add_rows(self.x, self.y).finish()
+        if relevance is not None:
+            if with_grad:
+                return self.model.evidence_grad(self.x, self.y, self.bound, ard=True)
+            return self.model.evidence(self.bound), None, None
         if with_grad:
             return self.model.evidence_grad(self.x, self.y, self.bound)
         return self.model.evidence(self.bound), None
+
+    def ard_terms(self):
+        return self.model.evidence_ard_terms()
 
     def terms(self):
         return self.model.evidence_terms()
@@ -339,30 +402,48 @@ class SparseEvidence:
 def tune_hyperparameters(kernel_fn, x_train, y_train, m: int, bound: str = "vfe", select: str = "greedy", steps: int = 50,
                          lr: float = 0.05, b_std_init=None, min_diag_reg: float = 1e-6, report=print, evaluator=None,
                          diag_reg: float = 1e-3, diag_reg_absolute_scale: bool = False, chunk_rows: int = 8192,
-                         jitter: float = 1e-8, candidates: int = 16384, seed: int = 10, inducing=None):
+                         jitter: float = 1e-8, candidates: int = 16384, seed: int = 10, inducing=None, ard: bool = False,
+                         ard_groups=None, relevance_init=None):
     """``mll.tune_hyperparameters`` on the sparse evidence: adaptive gradient steps over log sigma_w,l^2, log sigma_b,l^2 and
     log lambda, at O(N m^2) per step instead of O(N^3).  The m inducing rows are chosen once, by ``select_inducing`` with the
     starting kernel (or given as ``inducing``: indices into x_train), and held fixed.  ``bound``: ``"vfe"`` (Titsias' collapsed
     bound) or ``"dtc"``.  Reports ``"Step: %d, neg marginal likelihood: %f"`` after each step.  Returns ``(kernel_fn_tuned,
     diag_reg_tuned, history)``, ready for ``sparse_mse_ensemble``.  ``evaluator``: an object with ``evaluate(params, diag_reg,
     absolute, with_grad)`` to use instead of the GPU (tests drive the same loop with the NumPy reference); it brings its own
-    inducing rows.  A kernel_fn with feature groups or an input_scale is refused."""
+    inducing rows.  A kernel_fn with feature groups is refused, and without ``ard`` one with an input_scale.
+
+    ``ard``, ``ard_groups``, ``relevance_init``: as in ``mll.tune_hyperparameters`` -- one relevance s_k >= 0 per input feature
+    joins the tuned values as log s_k (start: ``relevance_init``, default the square of kernel_fn.input_scale, else 1), W_std of
+    Dense layer 0 is held fixed during the run, ``ard_groups`` ties features (labels, or ``"pairs"``), and the returned kernel_fn
+    carries ``input_scale = sqrt(s)``, ready for ``sparse_mse_ensemble``.  The result is normalised: the tuned relevances are
+    divided by their geometric mean g and W_std of Dense layer 0 is multiplied by sqrt(g) -- the same kernel, since a common factor
+    on s is the same thing as sigma_w,0^2 -- so the returned relevances have geometric mean 1 and compare across runs.  The inducing rows are chosen with the starting kernel (its
+    input_scale included) and held fixed as raw rows.  The evaluator then also takes ``relevance=`` and returns
+    ``(value, grad, grad_s)``."""
     from . import mll
     bound_code(bound)
     w0, b0, acts = mll.check_supported(kernel_fn)
-    check_evidence_spec(KernelSpec.of(kernel_fn))
+    spec = KernelSpec.of(kernel_fn)
+    check_evidence_spec(spec.replace(input_scale=None) if ard else spec)
     x, y = mll._train_arrays(x_train, y_train)
-    params = mll._Params(w0, b0, diag_reg, b_std_init, min_diag_reg)
+    if ard:
+        x, _, relevance_init = mll.split_input_scale(kernel_fn, x, True, relevance_init)
+    index = mll.relevance_groups(ard_groups, x.shape[1])[0] if ard else None
+    params = mll._Params(w0, b0, diag_reg, b_std_init, min_diag_reg, index, relevance_init)
     own = evaluator is None
     if own:
         if inducing is None:
             m = min(int(m), x.shape[0])
             inducing = select_inducing(x, m, kernel_fn, method=select, candidates=max(int(candidates), m), seed=seed)
-        evaluator = SparseEvidence(x, y, inducing, bound=bound, chunk_rows=chunk_rows, jitter=jitter)
+        evaluator = SparseEvidence(x, y, inducing, bound=bound, chunk_rows=chunk_rows, jitter=jitter, ard=bool(ard))
     try:
         raw, history = mll.tune_loop(params, evaluator, acts, diag_reg_absolute_scale, steps, lr, report)
     finally:
         if own:
             evaluator.close()
     w, b, lam, _ = params.unpack(raw)
-    return mll.rebuild_kernel_fn(w, b, acts), lam, history
+    rel = params.relevance(raw)
+    if rel is not None:
+        g = float(np.exp(np.mean(np.log(rel))))
+        rel, w = rel / g, [w[0] * math.sqrt(g)] + list(w[1:])
+    return mll.rebuild_kernel_fn(w, b, acts, rel), lam, history

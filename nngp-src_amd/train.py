@@ -158,11 +158,17 @@ def sparse_tune_kernel_fn(args, X_train, Y_train):
     the sparse model is for."""
     from . import sparse
     _, _, kernel_fn = kernel_fn_from_args(args)
+    ard = {}
+    if getattr(args, "sparse_tune_ard", False):  # --sparse_tune_ard: one relevance per input feature joins (nngp_sparse_ard.h)
+        groups = getattr(args, "ard_groups", "none")
+        ard = {"ard": True, "ard_groups": None if groups == "none" else groups}
     kernel_fn, diag_reg, _ = sparse.tune_hyperparameters(
         kernel_fn, X_train, Y_train, args.sparse, bound=getattr(args, "sparse_bound", "vfe"),
         select=getattr(args, "sparse_select", "greedy"), steps=args.sparse_tune, lr=args.tune_lr, b_std_init=args.b_std_init,
-        chunk_rows=getattr(args, "sparse_chunk", 8192), jitter=getattr(args, "sparse_jitter", 1e-8))
+        chunk_rows=getattr(args, "sparse_chunk", 8192), jitter=getattr(args, "sparse_jitter", 1e-8), **ard)
     print("Tuned W_std={} b_std={} diag_reg={}".format(list(kernel_fn.w_std), list(kernel_fn.b_std), diag_reg))
+    if ard:
+        print("Tuned relevances={}".format([float(v) for v in kernel_fn.input_scale ** 2]))
     return kernel_fn, diag_reg
 
 
@@ -239,6 +245,9 @@ def make_parser():
                         help="--sparse: steps of tuning W_std / b_std / diag_reg on the sparse model's evidence before the fit (0: off)")
     parser.add_argument("--sparse_bound", type=str, default="vfe", choices=("vfe", "dtc"),
                         help="--sparse_tune: the objective, Titsias' collapsed bound (vfe) or the DTC evidence")
+    parser.add_argument("--sparse_tune_ard", action='store_true',
+                        help="with --sparse M --sparse_tune STEPS: also tune one relevance per input feature on the sparse evidence "
+                             "(--ard_groups ties them; W_std of the first layer is fixed during the run)")
     parser.add_argument("--tune_lr", type=float, default=0.05, help="step size of --tune_hyper")
     parser.add_argument("--b_std_init", type=float, default=None, help="start of b_std for layers with b_std = 0 (--tune_hyper)")
     return parser
@@ -246,13 +255,15 @@ def make_parser():
 
 def parse_args(argv=None):
     """The command line with its conflicts checked: --sparse goes with --kernel_type nngp only, and not with --loo or --tune_*;
-    --sparse_tune needs --sparse."""
+    --sparse_tune needs --sparse, --sparse_tune_ard needs both."""
     parser = make_parser()
     args = parser.parse_args(argv)
     if args.sparse < 0:
         parser.error("argument --sparse: M must be >= 0")
     if args.sparse_tune < 0:
         parser.error("argument --sparse_tune: STEPS must be >= 0")
+    if args.sparse_tune_ard and (args.sparse <= 0 or args.sparse_tune <= 0):
+        parser.error("argument --sparse_tune_ard: needs --sparse M and --sparse_tune STEPS (it tunes relevances on the sparse evidence)")
     if args.sparse_tune > 0 and args.sparse <= 0:
         parser.error("argument --sparse_tune: needs --sparse M (it tunes the sparse model's evidence)")
     if args.sparse > 0:
