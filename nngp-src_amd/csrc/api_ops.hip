@@ -2,6 +2,7 @@
 // what tests/, scripts/ and the multi-GPU drivers call directly.
 #include "model.h"
 #include "gp_f64.h"
+#include "trsm_order.h"
 #include "../../include/nngp_i8s.h"
 
 extern "C" {

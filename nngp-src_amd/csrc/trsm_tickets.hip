@@ -16,7 +16,7 @@
 // dependencies are four monotone counters per r (device memory, zeroed before the launch): updates applied to tile (r, c),
 // split rows of B_J[r] written, diagonal tiles of X_J[r] done, split rows of X_J[r] written.
 //
-// Hang safety by construction: an item waits only for items with a LOWER ticket (the host's list scheduler starts an item only
+// Hang safety by construction: an item waits only for items with a LOWER ticket (the host's list scheduler, trsm_order.cpp, starts an item only
 // after the items it depends on have finished in its simulation, so they precede it in the table).  Every lower ticket is held by a
 // workgroup that is already running or has finished, so the lowest unfinished ticket can always proceed: no co-residency
 // assumption, any grid size.  Every spin loop is bounded in wall-clock time (s_memrealtime); on expiry the workgroup sets the
@@ -31,17 +31,21 @@
 // Tile arithmetic: the 128 x 128 form of the split-float16 product (256 threads = 4 waves 2 x 2, wave sub-tile 64 x 64 as 4 x 4
 // accumulators of v_mfma_f32_16x16x32_f16 with swapped operands, 2 x 32 KB LDS stages by global_load_lds_dwordx4, one barrier per
 // stage), two workgroups per compute unit so that one's waits, epilogue and split items run under the other's MFMAs.
+#include <stddef.h>
 #include <stdlib.h>
-#include <unistd.h>
 
 #include <algorithm>
-#include <functional>
-#include <queue>
 #include <vector>
 
 #include "common.h"
+#include "trsm_order.h"  // the item types IT_*, kQ, kMaxQ and the host's list scheduler
 
 namespace nngp {
+
+// the host builds the tables as TkItem, the kernel reads them as int4
+static_assert(sizeof(TkItem) == sizeof(int4) && offsetof(TkItem, word) == offsetof(int4, x) && offsetof(TkItem, r) == offsetof(int4, y) &&
+                  offsetof(TkItem, c) == offsetof(int4, z) && offsetof(TkItem, J) == offsetof(int4, w),
+              "TkItem must lie in memory like int4");
 
 namespace {
 
@@ -55,11 +59,8 @@ constexpr int TROW = 128;                // bytes per LDS row: 32 hi + 32 lo hal
 constexpr int TSTAGE = 2 * TT * TROW;    // A rows + B rows: 32 KB
 constexpr int64_t kLdp = 4096;           // bytes per split row (1024 k x 4 bytes), every plane buffer
 constexpr int kBs = 1024;                // block-column width
-constexpr int kQ = 4;                    // split items per (r, J): 32 rows each (8 waves x 4 rows)
 
-enum { IT_SB = 0, IT_D = 1, IT_SX = 2, IT_U = 3, IT_UB = 4, IT_UW = 5 };
 enum { SY_TICKET = 0, SY_ERROR = 1, SY_TICKETQ = 2, SY_COUNTERS = 16 };  // SY_TICKETQ .. + 7: one ticket counter per queue
-constexpr int kMaxQ = 8;
 
 struct TkParams {
     float* b;                 // right-hand sides [mt * 128, np], row stride ldb
@@ -765,225 +766,34 @@ __global__ __launch_bounds__(256) void k_transpose_1024(const float* __restrict_
     for (int i = 0; i < 4; ++i) dp[(int64_t)(c0 + ty + 8 * i) * kBs + n0 + tx] = tile[tx][ty + 8 * i];
 }
 
-// ---- host: the ticket order ----
-// List scheduling on `workers` simulated workgroups with rough item durations: an item enters the table when the simulation starts
-// it, i.e. after everything it depends on has FINISHED there -- so every dependency has a lower ticket whatever the real timing is.
-// Priority: earliest deadline first, the deadline of an item being the block column it feeds (diagonal chain items before the
-// updates of the next block column).  Updates come in two shapes: a 2 x 2 group of tiles takes every finished block column that is
-// waiting for it EXCEPT the two right before its own block, up to four at a time, as one 256 x 256 item (deep K where the chip is
-// throughput-bound); the last two block columns before a tile's own -- the updates on or next to the dependency chain -- are applied
-// tile by tile (128 x 128 items: four times the parallelism where only latency counts).  Tiles without a partner (odd row-tile count, odd tail)
-// take all their updates as 128 x 128 items.
-// merged: the chain update of a paired tile is a UW item (it waits for the split rows of the previous block B_J, not for X_J)
-// nq > 1: the workers are nq pools (the XCDs) with a table each.  A pair of row tiles belongs to 8 / (pairs) pools -- its bulk items are
-// dealt to them by column pair, its two chains to the first two -- so that everything that reads the split rows of X of one row pair
-// (1 MB per block column, read by every column pair's item) runs behind ONE L2, in the order in which it becomes ready: the items of one
-// block-column range over all column pairs are queued together and start together.  `queue_of` receives each item's pool; `out` stays
-// the global start order (an item's dependencies all precede it there).
-void tk_build_order(int mt, int nb, int tail_ct, bool backward, int workers, bool merged, std::vector<int4>& out, int nq = 1,
-                    std::vector<int>* queue_of = nullptr) {
-    const int ctiles = (nb - 1) * 8 + tail_ct;
-    auto ct_of = [&](int J) { return J == nb - 1 ? tail_ct : 8; };
-    auto pos_of = [&](int J) { return backward ? nb - 1 - J : J; };  // position of block column J in solve order (0 = solved first)
-    auto blk_at = [&](int pos) { return backward ? nb - 1 - pos : pos; };
-    const double t_split = 10.0, t_tile0 = 14.0, t_stage = 0.6, t_big0 = 24.0, t_bigstage = 1.6;  // us, from the stamps of GPU runs
-    int max_pan = 4;
-    if (const char* e = getenv("NNGP_TK_MAXPAN")) max_pan = std::max(1, std::min(4, atoi(e)));  // development aid
-    const bool no_big = getenv("NNGP_TK_NOBIG") != nullptr;                                      // development aid: 128 x 128 items only
-    enum { K_TILE = 0, K_PAIR = 1 };
-    struct Ready {
-        int key, c, r, type, J, kind;  // type IT_*; kind: what an update entry stands for
-        bool operator<(const Ready& o) const {  // priority_queue: largest first -> invert
-            if (key != o.key) return key > o.key;
-            if (c != o.c) return c > o.c;
-            if (r != o.r) return r > o.r;
-            return type > o.type;
-        }
-    };
-    struct Done {
-        double t;
-        int type, r, cq, J, npan;
-        int q = 0;
-        bool operator<(const Done& o) const { return t > o.t; }
-    };
-    if (nq < 1 || nq > kMaxQ) nq = 1;
-    std::vector<std::priority_queue<Ready>> ready_q((size_t)nq);
-    std::priority_queue<Done> running;
-    const int mt2p = mt / 2;
-    const int per_pair = (mt2p >= 1 && mt2p <= nq && nq % mt2p == 0) ? nq / mt2p : 1;  // pools per pair of row tiles
-    auto pool_of = [&](int type, int r, int c) -> int {  // r: row tile (IT_UB: first of the pair), c: column tile (split items: anything)
-        if (nq == 1) return 0;
-        const int rp = r / 2;
-        if (rp >= mt2p) return r % nq;  // the unpaired last row tile
-        const int base = (rp * per_pair) % nq;
-        if (type == IT_UB) return base + (c / 2) % per_pair;
-        return base + (r % 2) % per_pair;  // a row tile's chain (splits, diagonal products, 128 x 128 updates)
-    };
-    struct ReadyProxy {  // the single-queue code below pushes here
-        std::vector<std::priority_queue<Ready>>* q;
-        std::function<int(int, int, int)> pool;
-        void push(const Ready& it) { (*q)[(size_t)pool(it.type, it.r, it.c)].push(it); }
-    } ready{&ready_q, pool_of};
-    std::vector<int> up((size_t)mt * ctiles, 0);      // block columns applied to a tile (positions in solve order)
-    std::vector<char> busy((size_t)mt * ctiles, 0);   // an update of the tile is queued or running
-    std::vector<int> xs((size_t)mt * nb, 0), xd((size_t)mt * nb, 0), bs((size_t)mt * nb, 0), tiles_final((size_t)mt * nb, 0);
-    std::vector<int> xready((size_t)mt, 0);           // positions [0, xready[r]) have their split X
-    std::vector<int> bready((size_t)mt, 0);           // positions [0, bready[r]) have their split B (the merged chain update's operand)
-    const int mt2 = mt / 2, ct2 = ctiles / 2;         // 2 x 2 groups: row tiles (2 r2, 2 r2 + 1), column tiles (2 c2, 2 c2 + 1) -- same block (8 | 2 c2)
-    auto paired = [&](int r, int c) { return !no_big && r < 2 * mt2 && c < 2 * ct2 && (c / 8 != nb - 1 || (c % 8) + (c % 2 == 0 ? 1 : 0) < ct_of(nb - 1)); };
-    auto tile_id = [&](int r, int c) { return (size_t)r * ctiles + c; };
-    // the chain update of a tile: only its last block column is missing and that one is split
-    auto queue_final = [&](int r, int c) {
-        const size_t id = tile_id(r, c);
-        const int pc = pos_of(c / 8);
-        if (busy[id] || pc == 0 || up[id] != pc - 1 || (merged ? bready[r] : xready[r]) < pc) return;
-        busy[id] = 1;
-        ready.push(Ready{2 * pc - 1, c, r, merged ? IT_UW : IT_U, 0, K_TILE});
-    };
-    // the update before that (two block columns back): a 128 x 128 item as well -- as part of a 256 x 256 item (~100 us) it would sit
-    // between X_J and the chain update of the block after next, i.e. on the chain
-    auto queue_near = [&](int r, int c) {
-        const size_t id = tile_id(r, c);
-        const int pc = pos_of(c / 8);
-        if (busy[id] || pc < 2 || up[id] != pc - 2 || xready[r] < pc - 1) return;
-        busy[id] = 1;
-        ready.push(Ready{2 * pc - 1, c, r, IT_U, 0, K_TILE});
-    };
-    // an unpaired tile takes everything as 128 x 128 items
-    auto queue_single = [&](int r, int c) {
-        const size_t id = tile_id(r, c);
-        const int pc = pos_of(c / 8);
-        if (busy[id] || up[id] >= pc || up[id] >= xready[r]) return;
-        busy[id] = 1;
-        ready.push(Ready{2 * pc - 1, c, r, IT_U, 0, K_TILE});
-    };
-    auto queue_pair = [&](int r2, int c2) {
-        const int r = 2 * r2, c = 2 * c2;
-        const int pc = pos_of(c / 8);
-        const size_t id = tile_id(r, c);
-        const int p0 = up[id];
-        for (int dr = 0; dr < 2; ++dr)
-            for (int dc = 0; dc < 2; ++dc)
-                if (busy[tile_id(r + dr, c + dc)] || up[tile_id(r + dr, c + dc)] != p0) return;
-        const int xr = std::min(xready[r], xready[r + 1]);
-        if (std::min(pc - 2, xr) - p0 < 1) return;
-        for (int dr = 0; dr < 2; ++dr)
-            for (int dc = 0; dc < 2; ++dc) busy[tile_id(r + dr, c + dc)] = 1;
-        ready.push(Ready{2 * pc - 1, c, r, IT_UB, 0, K_PAIR});
-    };
-    auto requeue_tile = [&](int r, int c) {
-        if (paired(r, c)) {
-            queue_pair(r / 2, c / 2);
-            queue_near(r, c);
-            queue_final(r, c);
-        } else {
-            queue_single(r, c);
-        }
-    };
-    auto push_block_items = [&](int type, int r, int J) {
-        const int n = type == IT_D ? ct_of(J) : kQ;
-        for (int i = 0; i < n; ++i) ready.push(Ready{2 * pos_of(J), type == IT_D ? J * 8 + i : i, r, type, J, K_TILE});
-    };
-    for (int r = 0; r < mt; ++r) push_block_items(IT_SB, r, blk_at(0));
-    std::vector<int> free_q((size_t)nq, workers / nq > 0 ? workers / nq : 1);
-    double now = 0.0;
-    out.clear();
-    if (queue_of != nullptr) queue_of->clear();
-    for (;;) {
-        for (int q = 0; q < nq; ++q)
-        while (free_q[(size_t)q] > 0 && !ready_q[(size_t)q].empty()) {
-            int& free_workers = free_q[(size_t)q];
-            const Ready it = ready_q[(size_t)q].top();
-            ready_q[(size_t)q].pop();
-            int4 rec;
-            Done d{};
-            if (it.type == IT_UB) {
-                const int r = it.r, c = it.c, pc = pos_of(c / 8);
-                const int p0 = up[tile_id(r, c)];
-                int avail = std::min(pc - 2, std::min(xready[r], xready[r + 1])) - p0;
-                if (avail > max_pan) avail = max_pan;
-                if (backward && tail_ct != 8 && p0 == 0) avail = 1;  // a tail-width block column goes alone
-                const int plast = p0 + avail - 1;                    // latest block column of the item in solve order = first processed
-                rec = int4{IT_UB | (avail << 4), r / 2, c / 2, blk_at(plast)};
-                const int nk = (backward && tail_ct != 8 && p0 == 0) ? tail_ct * 4 : 32;
-                d = Done{now + t_big0 + t_bigstage * nk * avail, IT_UB, r, c, 0, avail};
-            } else if (it.type == IT_UW) {
-                const int pc = pos_of(it.c / 8);
-                const int Jsrc = blk_at(pc - 1);
-                rec = int4{IT_UW | (1 << 4), it.r, it.c, Jsrc};
-                d = Done{now + t_tile0 + t_stage * 4 * ct_of(Jsrc), IT_UW, it.r, it.c, 0, 1};
-            } else if (it.type == IT_U) {
-                const size_t id = tile_id(it.r, it.c);
-                const int pc = pos_of(it.c / 8);
-                const int p0 = up[id];
-                int avail = std::min(pc, xready[it.r]) - p0;
-                if (avail > max_pan) avail = max_pan;
-                if (backward && tail_ct != 8 && p0 == 0) avail = 1;
-                if (paired(it.r, it.c)) avail = 1;  // the near or the chain update of a paired tile: one block column
-                const int plast = p0 + avail - 1;
-                rec = int4{IT_U | (avail << 4), it.r, it.c, blk_at(plast)};
-                const int nk = (backward && tail_ct != 8 && p0 == 0) ? tail_ct * 4 : 32;
-                d = Done{now + t_tile0 + t_stage * nk * avail, IT_U, it.r, it.c, 0, avail};
-            } else {
-                rec = int4{it.type | (1 << 4), it.r, it.c, it.J};
-                double dur = t_split;
-                if (it.type == IT_D) {
-                    const int cl = it.c - it.J * 8;
-                    const int nk = backward ? (ct_of(it.J) - cl) * 4 : (cl + 1) * 4;
-                    dur = t_tile0 + t_stage * nk;
-                }
-                d = Done{now + dur, it.type, it.r, it.c, it.J, 1};
-            }
-            out.push_back(rec);
-            if (queue_of != nullptr) queue_of->push_back(q);
-            d.q = q;
-            running.push(d);
-            --free_workers;
-        }
-        if (running.empty()) break;
-        const Done d = running.top();
-        running.pop();
-        now = d.t;
-        ++free_q[(size_t)d.q];
-        const int r = d.r;
-        if (d.type == IT_SB) {
-            if (++bs[(size_t)r * nb + d.J] == kQ) {
-                push_block_items(IT_D, r, d.J);
-                bready[r] = pos_of(d.J) + 1;
-                if (merged && pos_of(d.J) + 1 < nb) {
-                    const int Jn = blk_at(pos_of(d.J) + 1);
-                    for (int c = Jn * 8; c < Jn * 8 + ct_of(Jn); ++c)
-                        if (paired(r, c)) queue_final(r, c);
-                }
-            }
-        } else if (d.type == IT_D) {
-            if (++xd[(size_t)r * nb + d.J] == ct_of(d.J)) push_block_items(IT_SX, r, d.J);
-        } else if (d.type == IT_SX) {
-            if (++xs[(size_t)r * nb + d.J] == kQ) {
-                xready[r] = pos_of(d.J) + 1;
-                for (int c = 0; c < ctiles; ++c)
-                    if (pos_of(c / 8) > pos_of(d.J)) requeue_tile(r, c);
-            }
-        } else {
-            const int nr = d.type == IT_UB ? 2 : 1;
-            for (int dr = 0; dr < nr; ++dr)
-                for (int dc = 0; dc < nr; ++dc) {
-                    const size_t id = tile_id(r + dr, d.cq + dc);
-                    up[id] += d.npan;
-                    busy[id] = 0;
-                }
-            for (int dr = 0; dr < nr; ++dr)
-                for (int dc = 0; dc < nr; ++dc) {
-                    const int rr = r + dr, cc = d.cq + dc, Jt = cc / 8;
-                    if (up[tile_id(rr, cc)] == pos_of(Jt)) {
-                        if (++tiles_final[(size_t)rr * nb + Jt] == ct_of(Jt)) push_block_items(IT_SB, rr, Jt);
-                    } else {
-                        requeue_tile(rr, cc);
-                    }
-                }
-        }
-    }
+// Development aids: block columns per update item (NNGP_TK_MAXPAN, 1 .. 4), 128 x 128 items only (NNGP_TK_NOBIG), the merged chain
+// operands never / always instead of by tk_prepare_inverses' rule (NNGP_TK_MERGE = 0 / 1).  Constants in the product library; only the
+// timing-knobs build reads them from the environment, once.
+struct TkDevSwitches {
+    TkOrderOptions order;
+    int merge = -1;  // -1: by the rule
+};
+const TkDevSwitches& tk_dev_switches() {
+#ifdef NNGP_TIMING_KNOBS
+    static const TkDevSwitches sw = [] {
+        TkDevSwitches v;
+        if (const char* e = getenv("NNGP_TK_MAXPAN")) v.order.max_pan = std::max(1, std::min(4, atoi(e)));
+        v.order.no_big = getenv("NNGP_TK_NOBIG") != nullptr;
+        if (const char* e = getenv("NNGP_TK_MERGE")) v.merge = atoi(e) != 0 ? 1 : 0;
+        return v;
+    }();
+#else
+    static const TkDevSwitches sw;
+#endif
+    return sw;
 }
+
+// what the item tables on the device were built for
+struct TkTableKey {
+    int mt = 0, nb = 0, tail_ct = 0;
+    int merged[2] = {-1, -1};
+    bool operator==(const TkTableKey& o) const { return mt == o.mt && nb == o.nb && tail_ct == o.tail_ct && merged[0] == o.merged[0] && merged[1] == o.merged[1]; }
+};
 
 }  // namespace
 
@@ -1003,7 +813,6 @@ struct TrsmTickets {
     float* w_iscale = nullptr;    // [2][nb_cap]
     unsigned* wmax = nullptr;     // [2][nb_cap]
     bool w_ready[2] = {false, false};
-    int key_merged[2] = {-1, -1};
     unsigned* amax = nullptr;     // [2][nb_cap]
     int* sync = nullptr;
     int64_t sync_ints = 0;
@@ -1013,8 +822,8 @@ struct TrsmTickets {
     int nq = 1;                   // queues of the item table: 8 (one per XCD) on a device with 8 XCDs of 32 compute units, else 1
     int q_off[2][kMaxQ + 1] = {};
     int nq_dir[2] = {1, 1};       // queues of the current tables
-    int key_mt = 0, key_nb = 0, key_tail = 0;
-    std::vector<int4> host_items[2];
+    TkTableKey key;               // ... and what they were built for
+    std::vector<TkItem> host_items[2];
     int* host_err = nullptr;      // pinned: error word of the last launches
     hipEvent_t ev_err = nullptr;
     bool err_pending = false;
@@ -1116,8 +925,8 @@ int tk_prepare_inverses(TrsmTickets* tk, const TriInv& ti, int64_t np, const flo
     // not by the operand traffic of its bulk: measured per predict of three solves after a fit, merged against plain, solves / step in ms --
     // N = 8192, M = 1024: 1.96 / 2.37 (step equal: the operands cost the fit 0.3 ms); N = 16384 NTK: 9.1 / 10.8, step -0.8; N = 32768: 13.6 /
     // 14.0 but step +0.7 (1 ms of operands per fit); N = 65536: 49.1 / 46.0; N = 10800, M = 3600: step +0.6.  Hence: row tiles x block columns.
-    static const char* merge_env = getenv("NNGP_TK_MERGE");  // (development aid: 0 never, 1 always)
-    const bool want = merge_env != nullptr ? atoi(merge_env) != 0 : (tk->m_cap / TT) * (int64_t)nb <= 192;
+    const int forced = tk_dev_switches().merge;
+    const bool want = forced >= 0 ? forced != 0 : (tk->m_cap / TT) * (int64_t)nb <= 192;
     if (l == nullptr || nb < 2 || !want) return 0;
     const int64_t blk = (int64_t)kBs * kBs;
     NNGP_HIP_CHECK(hipMemsetAsync(tk->wmax, 0, sizeof(unsigned) * 2 * tk->nb_cap, s));
@@ -1160,26 +969,6 @@ int tk_prepare_inverses(TrsmTickets* tk, const TriInv& ti, int64_t np, const flo
     return 0;
 }
 
-// the ticket table of a shape, four ints per item {type | panels << 4, r, c or q, J}, for the host-side proof that every item's
-// dependencies hold lower tickets (tests/test_host.py)
-int tk_order_export(int mt, int nb, int tail_ct, int backward, int workers, int merged, int queues, int32_t* out, int32_t* queue_of, int64_t cap,
-                    int64_t* count) {
-    NNGP_REQUIRE(mt >= 1 && nb >= 1 && tail_ct >= 1 && tail_ct <= 8 && workers >= 1 && count != nullptr && (queues == 1 || queues == kMaxQ),
-                 "trsm_ticket_order: bad shape");
-    std::vector<int4> items;
-    std::vector<int> qof;
-    tk_build_order(mt, nb, tail_ct, backward != 0, workers, merged != 0, items, queues, &qof);
-    *count = (int64_t)items.size();
-    if (out != nullptr) {
-        NNGP_REQUIRE((int64_t)items.size() <= cap, "trsm_ticket_order: %lld items, room for %lld", (long long)items.size(), (long long)cap);
-        for (size_t i = 0; i < items.size(); ++i) {
-            out[4 * i] = items[i].x; out[4 * i + 1] = items[i].y; out[4 * i + 2] = items[i].z; out[4 * i + 3] = items[i].w;
-            if (queue_of != nullptr) queue_of[i] = qof[i];
-        }
-    }
-    return 0;
-}
-
 bool tk_inverses_ready(const TrsmTickets* tk) { return tk != nullptr && tk->inv_ready; }
 void tk_invalidate_inverses(TrsmTickets* tk) { if (tk != nullptr) tk->inv_ready = false; }
 
@@ -1187,41 +976,35 @@ bool tk_usable(const TrsmTickets* tk, int64_t m, int64_t np) {
     return tk != nullptr && tk->inv_ready && m % TT == 0 && m >= TT && m <= tk->m_cap && np % TT == 0 && np <= tk->np_cap && np >= 2 * kBs;
 }
 
-// B[m, np] <- B L^-T (backward = false; sw.planes) or B L^-1 (backward = true; sw.planes_t) in one launch
-int tk_solve(TrsmTickets* tk, float* b, int64_t ldb, int64_t m, int64_t np, const SplitWork& sw, bool backward, hipStream_t s, int reserve_cus) {
-    NNGP_REQUIRE(tk_usable(tk, m, np), "tk_solve: not usable for m=%lld np=%lld", (long long)m, (long long)np);
-    NNGP_REQUIRE(sw.k_cap == kBs && (backward ? (sw.planes_t != nullptr && sw.lt_ready) : (sw.planes != nullptr && sw.l_ready)),
-                 "tk_solve: split copy of the factor not available");
-    NNGP_REQUIRE(ldb % 32 == 0 && ldb < (1LL << 26) && ((uintptr_t)b & 127) == 0, "tk_solve: right-hand sides must be 128-byte aligned rows");
-    const int mt = (int)(m / TT), nb = (int)((np + kBs - 1) / kBs);
-    const int tail_ct = (int)((np - (int64_t)(nb - 1) * kBs) / TT);
-    if (tk->key_mt != mt || tk->key_nb != nb || tk->key_tail != tail_ct || tk->key_merged[0] != (int)tk->w_ready[0] || tk->key_merged[1] != (int)tk->w_ready[1]) {
-        // a new shape (the first solve, or another batch size): the device may still read the old tables
-        NNGP_HIP_CHECK(hipDeviceSynchronize());
-        for (int dir = 0; dir < 2; ++dir) {
-            std::vector<int4> order;
-            std::vector<int> qof;
-            // (eight tables only for shapes whose launches fill the chip: every XCD then has workgroups drawing from its table)
-            const int nq = (tk->nq == kMaxQ && (int64_t)mt * nb >= 32) ? kMaxQ : 1;
-            tk->nq_dir[dir] = nq;
-            tk_build_order(mt, nb, tail_ct, dir == 1, tk->workers, tk->w_ready[dir], order, nq, &qof);
-            tk->key_merged[dir] = (int)tk->w_ready[dir];
-            NNGP_REQUIRE((int64_t)order.size() <= tk->items_cap, "tk_solve: item table overflow");
-            // the queues' tables one behind the other, each in the global start order
-            std::vector<int4>& tab = tk->host_items[dir];
-            tab.clear();
-            tab.reserve(order.size());
-            for (int q = 0; q < nq; ++q) {
-                tk->q_off[dir][q] = (int)tab.size();
-                for (size_t i = 0; i < order.size(); ++i)
-                    if (qof[i] == q) tab.push_back(order[i]);
-            }
-            for (int q = nq; q <= kMaxQ; ++q) tk->q_off[dir][q] = (int)tab.size();
-            tk->n_items[dir] = (int)tab.size();
-            NNGP_HIP_CHECK(hipMemcpy(tk->items[dir], tab.data(), sizeof(int4) * tab.size(), hipMemcpyHostToDevice));
-        }
-        tk->key_mt = mt; tk->key_nb = nb; tk->key_tail = tail_ct;
+// The item tables of both directions for a shape, on the device.  One entry: another batch size, or merged chain operands that
+// came or went, rebuilds and uploads both.
+static int tk_ensure_tables(TrsmTickets* tk, int mt, int nb, int tail_ct) {
+    TkTableKey key;
+    key.mt = mt; key.nb = nb; key.tail_ct = tail_ct;
+    key.merged[0] = (int)tk->w_ready[0]; key.merged[1] = (int)tk->w_ready[1];
+    if (tk->key == key) return 0;
+    // a new shape (the first solve, or another batch size): the device may still read the old tables
+    NNGP_HIP_CHECK(hipDeviceSynchronize());
+    tk->key = TkTableKey();  // (no table counts until both are up)
+    for (int dir = 0; dir < 2; ++dir) {
+        std::vector<TkItem> order;
+        std::vector<int> qof;
+        // (eight tables only for shapes whose launches fill the chip: every XCD then has workgroups drawing from its table)
+        const int nq = (tk->nq == kMaxQ && (int64_t)mt * nb >= 32) ? kMaxQ : 1;
+        tk->nq_dir[dir] = nq;
+        tk_build_order(mt, nb, tail_ct, dir == 1, tk->workers, tk->w_ready[dir], order, nq, &qof, tk_dev_switches().order);
+        NNGP_REQUIRE((int64_t)order.size() <= tk->items_cap, "tk_solve: item table overflow");
+        std::vector<TkItem>& tab = tk->host_items[dir];
+        tk_layout_tables(order, qof, nq, tab, tk->q_off[dir]);
+        tk->n_items[dir] = (int)tab.size();
+        NNGP_HIP_CHECK(hipMemcpy(tk->items[dir], tab.data(), sizeof(TkItem) * tab.size(), hipMemcpyHostToDevice));
     }
+    tk->key = key;
+    return 0;
+}
+
+// the kernel's argument for one solve of the shape the tables were built for
+static TkParams tk_params(const TrsmTickets* tk, float* b, int64_t ldb, const SplitWork& sw, bool backward) {
     const int dir = backward ? 1 : 0;
     TkParams P{};
     P.b = b; P.ldb = ldb;
@@ -1229,7 +1012,7 @@ int tk_solve(TrsmTickets* tk, float* b, int64_t ldb, int64_t m, int64_t np, cons
     P.l_stride = sw.col_stride;
     P.dinv_s = backward ? tk->tinv_s : tk->xinv_s;
     P.dinv_iscale = tk->inv_iscale + (backward ? tk->nb_cap : 0);
-    P.wplanes = tk->wplanes[backward ? 1 : 0];
+    P.wplanes = tk->wplanes[dir];
     P.w_iscale = tk->w_iscale + (backward ? tk->nb_cap : 0);
     P.planes_x = tk->planes_x; P.planes_d = tk->planes_d;
     P.p_stride = tk->m_cap * kLdp;
@@ -1240,12 +1023,44 @@ int tk_solve(TrsmTickets* tk, float* b, int64_t ldb, int64_t m, int64_t np, cons
     P.nq = tk->nq_dir[dir];
     for (int q = 0; q <= kMaxQ; ++q) P.q_off[q] = tk->q_off[dir][q];
     P.sync = tk->sync;
-    P.mt = mt; P.nb = nb; P.ctiles = (nb - 1) * 8 + tail_ct; P.tail_ct = tail_ct;
+    P.mt = tk->key.mt; P.nb = tk->key.nb; P.tail_ct = tk->key.tail_ct;
+    P.ctiles = (P.nb - 1) * 8 + P.tail_ct;
     P.l_iscale = 1.0f / sw.scale;
-    P.backward = backward ? 1 : 0;
+    P.backward = dir;
     P.spin_ticks = 200000000ULL;  // 2 s
     P.spin_max = 1u << 22;        // > 4 s of polls at ~1 us each
     P.fault_ticket = -1;
+    return P;
+}
+
+#ifdef NNGP_TIMING_KNOBS
+// timing study: waits for the launch and prints what its workgroups spent per item type
+static void tk_print_stamps(bool backward, int mt, int nb) {
+    unsigned long long h[28];
+    (void)hipDeviceSynchronize();
+    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_tk_stamps), sizeof(h)) != hipSuccess) return;
+    static const char* names[6] = {"SB", "D", "SX", "U", "UB", "UW"};
+    fprintf(stderr, "tk stamps (%s, mt %d nb %d): %llu workgroups, mean kernel time per workgroup %.1f us\n", backward ? "backward" : "forward", mt, nb, h[25],
+            h[25] ? 0.01 * (double)h[24] / (double)h[25] : 0.0);
+    for (int t = 0; t < 6; ++t)
+        fprintf(stderr, "   %-2s items %6llu: wait %.2f us  body %.2f us  publish %.2f us per item; share of workgroup time: wait %.1f %% body %.1f %% publish %.1f %%\n", names[t],
+                h[t * 4 + 3], h[t * 4 + 3] ? 0.01 * h[t * 4] / h[t * 4 + 3] : 0.0, h[t * 4 + 3] ? 0.01 * h[t * 4 + 1] / h[t * 4 + 3] : 0.0,
+                h[t * 4 + 3] ? 0.01 * h[t * 4 + 2] / h[t * 4 + 3] : 0.0, 100.0 * h[t * 4] / (double)h[24], 100.0 * h[t * 4 + 1] / (double)h[24], 100.0 * h[t * 4 + 2] / (double)h[24]);
+    unsigned long long z[28] = {};
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_tk_stamps), z, sizeof(z));
+}
+#endif
+
+// B[m, np] <- B L^-T (backward = false; sw.planes) or B L^-1 (backward = true; sw.planes_t) in one launch
+int tk_solve(TrsmTickets* tk, float* b, int64_t ldb, int64_t m, int64_t np, const SplitWork& sw, bool backward, hipStream_t s, int reserve_cus) {
+    NNGP_REQUIRE(tk_usable(tk, m, np), "tk_solve: not usable for m=%lld np=%lld", (long long)m, (long long)np);
+    NNGP_REQUIRE(sw.k_cap == kBs && (backward ? (sw.planes_t != nullptr && sw.lt_ready) : (sw.planes != nullptr && sw.l_ready)),
+                 "tk_solve: split copy of the factor not available");
+    NNGP_REQUIRE(ldb % 32 == 0 && ldb < (1LL << 26) && ((uintptr_t)b & 127) == 0, "tk_solve: right-hand sides must be 128-byte aligned rows");
+    const int mt = (int)(m / TT), nb = (int)((np + kBs - 1) / kBs);
+    const int tail_ct = (int)((np - (int64_t)(nb - 1) * kBs) / TT);
+    NNGP_TRY(tk_ensure_tables(tk, mt, nb, tail_ct));
+    TkParams P = tk_params(tk, b, ldb, sw, backward);
     if (const char* f = getenv("NNGP_TK_FAULT")) {  // test hook (tests/test_gpu_parity.py): lose one item's completion, give up after 50 ms
         P.fault_ticket = atoi(f);
         P.spin_ticks = 5000000ULL;
@@ -1265,54 +1080,8 @@ int tk_solve(TrsmTickets* tk, float* b, int64_t ldb, int64_t m, int64_t np, cons
     NNGP_HIP_CHECK(hipEventRecord(tk->ev_err, s));
     tk->err_pending = true;
 #ifdef NNGP_TIMING_KNOBS
-    if (getenv("NNGP_TK_STAMPS") != nullptr) {
-        unsigned long long h[28];
-        (void)hipDeviceSynchronize();
-        if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_tk_stamps), sizeof(h)) == hipSuccess) {
-            static const char* names[6] = {"SB", "D", "SX", "U", "UB", "UW"};
-            fprintf(stderr, "tk stamps (%s, mt %d nb %d): %llu workgroups, mean kernel time per workgroup %.1f us\n", backward ? "backward" : "forward", mt, nb, h[25],
-                    h[25] ? 0.01 * (double)h[24] / (double)h[25] : 0.0);
-            for (int t = 0; t < 6; ++t)
-                fprintf(stderr, "   %-2s items %6llu: wait %.2f us  body %.2f us  publish %.2f us per item; share of workgroup time: wait %.1f %% body %.1f %% publish %.1f %%\n", names[t],
-                        h[t * 4 + 3], h[t * 4 + 3] ? 0.01 * h[t * 4] / h[t * 4 + 3] : 0.0, h[t * 4 + 3] ? 0.01 * h[t * 4 + 1] / h[t * 4 + 3] : 0.0,
-                        h[t * 4 + 3] ? 0.01 * h[t * 4 + 2] / h[t * 4 + 3] : 0.0, 100.0 * h[t * 4] / (double)h[24], 100.0 * h[t * 4 + 1] / (double)h[24], 100.0 * h[t * 4 + 2] / (double)h[24]);
-            unsigned long long z[28] = {};
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(g_tk_stamps), z, sizeof(z));
-        }
-    }
+    if (getenv("NNGP_TK_STAMPS") != nullptr) tk_print_stamps(backward, mt, nb);
 #endif
-    if (getenv("NNGP_TK_DUMP") != nullptr && !backward) {  // development aid: what the split rows of block column 0 hold after the solve
-        (void)hipDeviceSynchronize();
-        std::vector<_Float16> h(8 * 2048);
-        for (int row : {6, 7, 14, 15, 135}) {
-            if (hipMemcpy(h.data(), tk->planes_d + (int64_t)row * kLdp, kLdp, hipMemcpyDeviceToHost) != hipSuccess) break;
-            int bad = 0, firstbad = -1;
-            for (int kb = 0; kb < 32; ++kb)
-                for (int e = 0; e < 64; ++e) {
-                    const float v = (float)h[kb * 64 + e];
-                    if (!(fabsf(v) <= 16384.0f)) { ++bad; if (firstbad < 0) firstbad = kb * 64 + e; }
-                }
-            fprintf(stderr, "tk dump: planes_d[0] row %d: %d halfs out of range (first at %d); kb 0: %g %g, kb 24: %g %g %g %g, kb 31: %g\n", row, bad, firstbad,
-                    (double)(float)h[0], (double)(float)h[1], (double)(float)h[24 * 64], (double)(float)h[24 * 64 + 1], (double)(float)h[24 * 64 + 8], (double)(float)h[24 * 64 + 32], (double)(float)h[31 * 64]);
-        }
-    }
-    if (getenv("NNGP_TK_WATCH") != nullptr) {  // development aid: watch the launch from a second stream
-        hipStream_t w = nullptr;
-        std::vector<int> h((size_t)used);
-        if (hipStreamCreateWithFlags(&w, hipStreamNonBlocking) == hipSuccess) {
-            for (int it = 0; it < 40; ++it) {
-                if (hipEventQuery(tk->ev_err) == hipSuccess) { fprintf(stderr, "tk watch: launch finished (poll %d), error word 0x%x\n", it, tk->host_err[0]); break; }
-                (void)hipGetLastError();
-                usleep(250000);
-                if (hipMemcpyAsync(h.data(), tk->sync, sizeof(int) * (size_t)used, hipMemcpyDeviceToHost, w) != hipSuccess || hipStreamSynchronize(w) != hipSuccess) break;
-                long long sx = 0, sd = 0, sb = 0, su = 0;
-                for (int i = 0; i < mt * nb; ++i) { sd += h[SY_COUNTERS + i]; sx += h[SY_COUNTERS + mt * nb + i]; sb += h[SY_COUNTERS + 2 * mt * nb + i]; }
-                for (int i = 0; i < mt * P.ctiles; ++i) su += h[SY_COUNTERS + 3 * mt * nb + i];
-                fprintf(stderr, "tk watch %d: ticket %d / %d, error 0x%x, done: D %lld SX %lld SB %lld U-panels %lld\n", it, h[0], P.n_items, h[1], sd, sx, sb, su);
-            }
-            (void)hipStreamDestroy(w);
-        }
-    }
     return 0;
 }
 

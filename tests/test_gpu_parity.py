@@ -1248,3 +1248,39 @@ def test_persistent_solves_with_one_table_per_xcd_return_the_same_bits():
         model.close()
     assert np.isfinite(out[0][0]).all() and np.isfinite(out[0][1]).all()
     assert np.array_equal(out[0][0], out[1][0]) and np.array_equal(out[0][1], out[1][1])
+
+
+def test_persistent_solves_rebuild_their_tables_when_the_batch_changes():
+    """The item tables of a persistent solve are built for one batch size (csrc/trsm_tickets.hip, tk_ensure_tables: one entry, keyed by
+    row tiles, block columns, tail and merged operands).  1024 rows, then 768, then the same 1024 again: 768 x 9344 entries are still
+    above the threshold of the float16-pipe solves, so the second call swaps the tables of both directions for those of six row tiles and
+    the third swaps them back.  The tables are a pure function of the shape, so the first and third results must agree bit for bit; the
+    768-row results must be right -- each triangular solve against scipy's on the float64 copy of the factor, the backward one from the
+    forward result it was given, with the neighbouring tests' bound (L^T is as well conditioned as L, the kernel is the same) -- and no
+    call may run into the bounded waits."""
+    import scipy.linalg as sla
+    n = 9300
+    x, y = synth.synthetic_queries(n, 24, seed=53)
+    model = GPModel(n, 24, [1.0, 1.0], [0.0, 0.0], diag_reg=1e-3).fit(x, y)
+    a32, _ = model.factor_buffers()
+    L = torch.tril(a32[:n, :n]).double().cpu().numpy()
+    B = np.random.default_rng(5).standard_normal((1024, n)).astype(np.float32)
+    out = []
+    try:
+        for rows in (1024, 768, 1024):
+            t0 = time.perf_counter()
+            fwd = model.apply_factor(torch.from_numpy(B[:rows].copy()).to(G.dev())).cpu().numpy()
+            both = model.apply_factor(torch.from_numpy(B[:rows].copy()).to(G.dev()), both_halves=True).cpu().numpy()
+            assert time.perf_counter() - t0 < 5.0, rows
+            assert np.isfinite(fwd).all() and np.isfinite(both).all(), rows
+            out.append((fwd, both))
+    finally:
+        model.close()
+    assert np.array_equal(out[0][0], out[2][0]) and np.array_equal(out[0][1], out[2][1])
+    fwd, both = (v.astype(np.float64) for v in out[1])
+    fwd_ref = sla.solve_triangular(L, B[:768].astype(np.float64).T, lower=True).T
+    both_ref = sla.solve_triangular(L, fwd.T, lower=True, trans="T").T
+    print("768 rows: forward %.3e, backward %.3e (relative Frobenius)" % (np.linalg.norm(fwd - fwd_ref) / np.linalg.norm(fwd_ref),
+                                                                          np.linalg.norm(both - both_ref) / np.linalg.norm(both_ref)))
+    assert np.linalg.norm(fwd - fwd_ref) <= 2e-3 * np.linalg.norm(fwd_ref)
+    assert np.linalg.norm(both - both_ref) <= 2e-3 * np.linalg.norm(both_ref)

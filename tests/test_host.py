@@ -28,8 +28,12 @@ def test_library_loads_and_exports_every_declared_symbol():
         assert hasattr(lib, name), name
     assert not hasattr(lib, "nngp_debug_set"), "the product library must not export the timing knobs"
     product = open(_lib.LIB_PATH, "rb").read()  # ... nor read the posterior's scheduling aids from the environment
-    for name in (b"NNGP_TK_GATE", b"NNGP_TK_RESERVE", b"NNGP_TK_CUTSTREAM"):
+    scheduler_aids = (b"NNGP_TK_MAXPAN", b"NNGP_TK_NOBIG", b"NNGP_TK_MERGE")  # ... nor the list scheduler's (csrc/trsm_tickets.hip: tk_dev_switches)
+    for name in (b"NNGP_TK_GATE", b"NNGP_TK_RESERVE", b"NNGP_TK_CUTSTREAM") + scheduler_aids + (b"NNGP_TK_DUMP", b"NNGP_TK_WATCH", b"NNGP_TK_STAMPS"):
         assert name not in product, name
+    knobs_text = open(_lib.KNOBS_LIB_PATH, "rb").read()
+    for name in scheduler_aids:
+        assert name in knobs_text, name
     knobs = _lib.load(knobs=True)
     for name in _lib.ABI_SYMBOLS + ("nngp_debug_set",):
         assert hasattr(knobs, name), name
@@ -498,7 +502,7 @@ def test_persistent_solve_queues_drain_whoever_draws_from_them(mt, nb, tail):
             if word & 15 == 4 and mt // 2 in (1, 2, 4, 8):
                 per = 8 // (mt // 2)
                 assert r * per <= q < (r + 1) * per, "a bulk item outside the queues of its pair of row tiles"
-        tables = [[i for i in range(n) if qof[i] == q] for q in range(8)]   # (2): by construction of the device tables (tk_solve)
+        tables = [[i for i in range(n) if qof[i] == q] for q in range(8)]   # (2): how tk_layout_tables lays the device tables out (held to this by tests/test_trsm_order_host.py)
         for workers_per_q in ([1] * 8, [4] * 8, [32] * 8, [2, 1, 3, 1, 1, 5, 1, 2]):
             state = _TicketState(mt, nb, tail, bool(backward))
             head = [0] * 8
