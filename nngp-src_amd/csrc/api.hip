@@ -374,15 +374,7 @@ int nngp_model_reserve(nngp_model* m, int64_t rows, int32_t cov_mode) {
     if (m->var_refine >= 1 || m->get == NNGP_GET_NTK) NNGP_TRY(ensure_refine_capacity(m, mp));
     const bool split_path = m->split.planes != nullptr && mp <= m->split.mb_cap && mp >= 256 && mp * m->np_cap >= 7000000;
     if (!split_path) NNGP_TRY(ensure_lt_alloc(m));
-    if (m->np_cap >= 2048 && mp >= 256 && !m->i8_unavailable && (m->var_refine >= 1 || m->get == NNGP_GET_NTK)) {
-        if (cov_mode == NNGP_COV_FULL && m->np_cap >= 4096 && mp >= 512) m->i8_want_fine = true;
-        const int rc = ensure_i8s(m, mp, m->i8.k, i8s_planes_policy(m));
-        if (rc != 0 && rc != 1) return rc;
-        if (rc == 0 && m->i8_guard == nullptr) {  // the guard's word and its pinned mirror (level-1 variances)
-            NNGP_TRY(dev_alloc(&m->i8_guard, 1));
-            NNGP_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&m->i8_guard_host), sizeof(unsigned long long), hipHostMallocDefault));
-        }
-    }
+    NNGP_TRY(i8s_reserve(m, mp, cov_mode));
     if (cov_mode == NNGP_COV_FULL) NNGP_TRY(ensure_full_cov_capacity(m, rows));
     return 0;
 }
@@ -438,9 +430,7 @@ int nngp_model_build_rows(nngp_model* m, int64_t row_begin, int64_t row_end, voi
     m->a32_complete = false;
     m->k64_partial = false;
     m->k64_symmetric = a.sym != 0;
-    m->i8.k.ready = false;
-    m->i8_checked = m->i8_distrusted = false;
-    m->i8_guard_pending = false;
+    i8s_kernel_changed(m);
     if (a.sym) {  // whole matrix in one build: the float32 factorisation input falls out of the same epilogue
         if (m->get == NNGP_GET_NNGP) { a.nngp32 = m->a32; a.diag_add_nngp32 = m->reg; }
         else { a.ntk32 = m->a32; a.diag_add_ntk32 = m->reg; }
@@ -457,7 +447,7 @@ int nngp_model_build_rows(nngp_model* m, int64_t row_begin, int64_t row_end, voi
     if (aux_too) {
         NNGP_TRY(launch_zero_pad_f64(m->kaux64, m->np, m->n, m->np, s));
         m->aux_ready = true;
-        m->i8.aux.ready = false;
+        m->i8.work.aux.ready = false;
     }
     NNGP_TRY(launch_zero_pad_f64(m->k64, m->ld, m->n, m->np, s));  // float64 GEMMs read the padded matrix
     m->built = true;  // the caller vouches for the remaining rows (all-gather) before factor
@@ -646,9 +636,7 @@ int nngp_model_append(nngp_model* m, const double* x_new, const double* y_new, i
     m->solved = false;
     m->solve_pending = false;
     m->serving_ready = false;
-    m->i8.k.ready = false;
-    m->i8_checked = m->i8_distrusted = false;
-    m->i8_guard_pending = false;
+    i8s_kernel_changed(m);
     // 2. kernel rows [n0, n1) against all n1 rows, their mirror image, and the new padding
     BuildArgs a{};
     a.x1 = m->x; a.x2 = m->x; a.q1 = m->q; a.q2 = m->q;
@@ -859,35 +847,17 @@ int nngp_model_update_timer_read(nngp_model* m, int64_t* launches, double* ms_to
 
 int nngp_model_residual_timer(nngp_model* m, int32_t enable) {
     NNGP_REQUIRE(m != nullptr, "residual_timer: NULL model");
-    m->i8.timed = enable != 0;
-    m->i8.t_count = 0;
-    return 0;
+    return i8s_timer_enable(m, enable);
 }
 
 int nngp_model_residual_timer_read(nngp_model* m, int64_t* launches, double* ms_total, double* flops_total, double* int8_ops_total) {
     NNGP_REQUIRE(m != nullptr, "residual_timer_read: NULL model");
-    I8Work& w = m->i8;
-    double ms = 0.0, fl = 0.0, ops = 0.0;
-    for (int t = 0; t < w.t_count; ++t) {
-        NNGP_HIP_CHECK(hipEventSynchronize(w.t1[t]));
-        float e = 0.0f;
-        NNGP_HIP_CHECK(hipEventElapsedTime(&e, w.t0[t], w.t1[t]));
-        ms += e;
-        fl += w.t_flops[t];
-        ops += w.t_ops[t];
-    }
-    if (launches) *launches = w.t_count;
-    if (ms_total) *ms_total = ms;
-    if (flops_total) *flops_total = fl;
-    if (int8_ops_total) *int8_ops_total = ops;
-    w.t_count = 0;
-    return 0;
+    return i8s_timer_read(m, launches, ms_total, flops_total, int8_ops_total);
 }
 
 int nngp_model_trsm_timer(nngp_model* m, int32_t enable) {
     NNGP_REQUIRE(m != nullptr, "trsm_timer: NULL model");
-    m->trsm_t.timed = enable != 0;
-    m->trsm_t.count = 0;
+    m->trsm_t.enable(enable != 0);
     return 0;
 }
 
@@ -895,13 +865,8 @@ int nngp_model_trsm_timer_read(nngp_model* m, int64_t* solves, double* ms_total,
     NNGP_REQUIRE(m != nullptr, "trsm_timer_read: NULL model");
     auto& w = m->trsm_t;
     double ms = 0.0, fl = 0.0;
-    for (int t = 0; t < w.count; ++t) {
-        NNGP_HIP_CHECK(hipEventSynchronize(w.t1[t]));
-        float e = 0.0f;
-        NNGP_HIP_CHECK(hipEventElapsedTime(&e, w.t0[t], w.t1[t]));
-        ms += e;
-        fl += w.flops[t];
-    }
+    NNGP_TRY(w.read(&ms));
+    for (int t = 0; t < w.count; ++t) fl += m->trsm_flops[t];
     if (solves) *solves = w.count;
     if (ms_total) *ms_total = ms;
     if (flops_total) *flops_total = fl;
@@ -911,17 +876,7 @@ int nngp_model_trsm_timer_read(nngp_model* m, int64_t* solves, double* ms_total,
 
 int nngp_model_residual_floor(nngp_model* m, double* ratio, int32_t* distrusted) {
     NNGP_REQUIRE(m != nullptr, "residual_floor: NULL model");
-    if (m->i8_guard_pending && m->ev_guard != nullptr) {  // the last level-1 batch's own estimate: wait for it and fold it in, so that a
-        NNGP_HIP_CHECK(hipEventSynchronize(m->ev_guard));  // caller can ask after a batch whether THAT batch tripped the guard
-        double r = 0.0;
-        memcpy(&r, m->i8_guard_host, sizeof(double));
-        m->i8_guard_pending = false;
-        if (r > m->i8_floor_ratio) m->i8_floor_ratio = r;
-        if (!(r <= kI8FloorThr)) m->i8_distrusted = true;
-    }
-    if (ratio) *ratio = m->i8_checked ? m->i8_floor_ratio : -1.0;
-    if (distrusted) *distrusted = m->i8_distrusted ? 1 : 0;
-    return 0;
+    return i8s_residual_floor(m, ratio, distrusted);
 }
 
 int nngp_model_update_timer_bytes(nngp_model* m, double* bytes_total) {

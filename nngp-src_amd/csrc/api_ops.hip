@@ -226,7 +226,7 @@ int nngp_gemm_nt_i8s(double* c, int64_t ldc, const double* cin, int64_t ldcin, c
 }
 
 // ---- include/nngp_i8s.h: the launches of the int8 residual pipeline without a model object (tests/test_gpu_i8s.py) ----
-// i8s_cut_planes and i8s_product_rows (api_predict.hip) take their buffers, events, timers and the alpha CG's gate from nngp_model;
+// i8s_cut_planes and i8s_product_rows (residual_i8.hip) take their buffers, events, timers and the alpha CG's gate from nngp_model;
 // the operators below issue the same launch_i8s_* / launch_gemm_nt_i8s calls in the same order on a workspace of their own.
 int nngp_i8s_cut_rows(const double* src, int64_t ld, int64_t rows, int64_t cols, int32_t ns, const double* scale_in, double* scale_out,
                       int8_t* planes, int64_t ldp, double* writeback, void* stream) {

@@ -1,5 +1,5 @@
-// The posterior half of the C ABI: workspaces of a predict, the consumers of the factor (blocked solves, refinement sweeps, the int8
-// residual products), nngp_model_prepare_serving / _predict / _apply_factor.  Reference: predict_fn(x_test, get, compute_cov),
+// The posterior half of the C ABI: workspaces of a predict, the consumers of the factor (blocked solves, refinement sweeps; their int8
+// residual products: residual_i8.hip), nngp_model_prepare_serving / _predict / _apply_factor.  Reference: predict_fn(x_test, get, compute_cov),
 // train.py:157-158, estimator.py:66-67.
 #include "model.h"
 
@@ -127,216 +127,6 @@ int ensure_lt_split(nngp_model* m, hipStream_t s) {
 }
 
 
-// ---- float64-grade residual products on the int8 matrix pipe (gemm_i8s.hip) ----
-constexpr int64_t kI8RowBlock = 2048;  // right-hand-side rows per pass (bounds the int32 partial buffer)
-
-// Where it pays (profiles/r3_i8s_crossover.jsonl, predict with the diagonal variance, float64 / int8 residual, ms): a predict that also
-// has to cut the planes of K (the first after a fit) wins from two 128-row tiles of right-hand sides on -- N = 2048, M = 256: 0.57 /
-// 0.50; N = 8192: M = 128 2.04 / 2.39, M = 256 2.45 / 2.56, M = 512 3.63 / 3.06, M = 1024 5.02 / 3.99; N = 16384, M = 1024: 15.5 / 11.4
-// -- later predicts on the same fit from any size on (N = 16384, M = 128: 4.51 / 4.42).  Debug key 5 = 50: float64 matrix pipe instead.
-bool use_i8s(const nngp_model* m, int64_t mp) {
-    if (m->i8_suspended || m->i8_unavailable || m->i8_distrusted) return false;
-    if (NNGP_KNOB(5) == 54) return true;  // timing experiment: at any size (scripts/i8s_crossover.py)
-    return m->np >= 2048 && mp >= 256 && NNGP_KNOB(5) != 50;
-}
-
-// Two grades of the product.  COARSE: 3 x 5 planes (z ROUNDED to its three and written back, round 4; 5 x 5 before), pairs with
-// ia + ib <= 4 (12 exact plane products, 15 before; error ~2^-32 sqrt(N) of the row maxima, all of it from the kernel's side now)
-// -- for a FIRST residual.  FINE: 7 x 7 planes, ia + ib <= 6 (28 products; ~2^-48 sqrt(N): what the float64 matrix pipe
-// delivers; since late round 4 z is ROUNDED to five planes there as well and written back: 5 x 7 planes, 25 products, the iterate
-// moves by 9e-13 of its row maximum) -- for the later residuals and the NTK's W = Z K_dd, where the coarse floor would show (see residual_rows); 28 products
-// still cost 3/4 of the float64 product at N = 32768.  A model that will ask for FINE products (NTK fits, covariance levels >= 2)
-// has its kernel matrix cut into 7 planes once; coarse products then read the first five of them.
-enum { I8_COARSE = 0, I8_FINE = 1 };
-constexpr int kI8FinePlanes = 7, kI8FineCut = 6;
-constexpr int kI8CoarseZPlanes = 3;  // a first residual's z is rounded to three digits and written back (i8s_product_rows)
-constexpr int kI8FineZPlanes = 5;    // a later residual's z (an iterate good to ~1e-8) and the NTK's final Z: rounded to 40 bits below the row maximum (9e-13 of it)
-
-// FINE pays later than COARSE (28 against 15 products): from N = 4096 and four 128-row tiles of right-hand sides on.  Debug key 5 = 57: off.
-bool use_i8s_fine(const nngp_model* m, int64_t mp) { return use_i8s(m, mp) && m->np >= 4096 && mp >= 512 && NNGP_KNOB(5) != 57; }
-// (i8_want_fine: a predict of this model has needed a FINE product before -- a full covariance at level 1 is promoted to level 2, a weak
-// fit's rows continue with later residuals -- so the planes are cut seven deep from the start instead of being thrown away, reallocated
-// and cut again in the middle of a predict)
-int i8s_planes_policy(const nngp_model* m) {
-    return (m->get == NNGP_GET_NTK || m->var_refine >= 2 || m->i8_want_fine) && NNGP_KNOB(5) != 57 ? kI8FinePlanes : 5;
-}
-
-
-// Workspace of the int8 path: `planes` N^2 bytes of digit planes of the kernel matrix `pk` + the planes and exact plane products of
-// one block of rows.  Returns 1 -- and the model stays on the float64 pipe from then on -- when the device has no room for them (a
-// kernel matrix that fills most of the 288 GB leaves none): the int8 path is an accelerator, not a requirement.
-int ensure_i8s(nngp_model* m, int64_t mp, I8Planes& pk, int planes) {
-    I8Work& w = m->i8;
-    if (NNGP_KNOB(5) == 51) { w.ns_k = w.ns_z = 4; w.cut = 3; }
-    else if (NNGP_KNOB(5) == 52) { w.ns_k = w.ns_z = 6; w.cut = 5; }
-    else { w.ns_k = 5; w.ns_z = NNGP_KNOB(5) == 58 ? 5 : kI8CoarseZPlanes; w.cut = 4; }
-    if (planes < w.ns_k) planes = w.ns_k;
-    w.k_rows = round_up(m->np_cap, 256);
-    auto give_up = [&]() -> int {
-        dev_free(m->i8.k.planes); dev_free(m->i8.k.scale); dev_free(m->i8.aux.planes); dev_free(m->i8.aux.scale);
-        dev_free(w.zplanes); dev_free(w.zscale); dev_free(w.partial); dev_free(w.rowpart);
-        w.rowpart_rows = 0;
-        m->i8.k.ready = m->i8.aux.ready = false;
-        m->i8.k.alloc_planes = m->i8.aux.alloc_planes = 0;
-        w.z_rows = 0;
-        w.z_planes = 0;
-        m->i8_unavailable = true;
-        return 1;
-    };
-    if (pk.alloc_planes < planes) {
-        NNGP_HIP_CHECK(hipDeviceSynchronize());
-        dev_free(pk.planes); dev_free(pk.scale);
-        pk.alloc_planes = 0;
-        if (!soft_alloc(&pk.planes, planes * w.k_rows * m->np_cap) || !soft_alloc(&pk.scale, m->np_cap + 1)) return give_up();
-        NNGP_HIP_CHECK(hipMemset(pk.planes, 0, (size_t)(planes * w.k_rows * m->np_cap)));
-        pk.alloc_planes = planes;
-        pk.ready = false;
-    }
-    if (mp > w.rowpart_rows) {
-        NNGP_HIP_CHECK(hipDeviceSynchronize());
-        dev_free(w.rowpart);
-        w.rowpart_rows = 0;
-        NNGP_TRY(dev_alloc(&w.rowpart, mp * i8s_col_blocks(m->np_cap) * 4));
-        w.rowpart_rows = mp;
-    }
-    if (w.counters == nullptr) {
-        NNGP_TRY(dev_alloc(&w.counters, 16));
-        NNGP_HIP_CHECK(hipMemset(w.counters, 0, 16 * sizeof(int)));
-    }
-    const int64_t rows = mp < kI8RowBlock ? mp : kI8RowBlock;
-    if (rows > w.z_rows || planes > w.z_planes) {
-        NNGP_HIP_CHECK(hipDeviceSynchronize());
-        dev_free(w.zplanes); dev_free(w.zscale); dev_free(w.partial);
-        const int64_t nr = rows > w.z_rows ? rows : w.z_rows;
-        const int np_ = planes > w.z_planes ? planes : w.z_planes;
-        w.z_rows = 0;
-        w.z_planes = 0;
-        if (!soft_alloc(&w.zplanes, np_ * (nr + 256) * m->np_cap) || !soft_alloc(&w.zscale, nr) ||
-            !soft_alloc(&w.partial, i8s_chunks(m->np_cap) * np_ * nr * m->np_cap))  // diagonals = cut + 1 <= planes
-            return give_up();
-        NNGP_HIP_CHECK(hipMemset(w.zplanes, 0, (size_t)(np_ * (nr + 256) * m->np_cap)));
-        w.z_rows = nr;
-        w.z_planes = np_;
-    }
-    return 0;
-}
-
-// the digit planes of a kernel matrix (as many as were allocated for it).  It is positive semi-definite: row i is bounded by
-// sqrt(K_ii max_j K_jj) -- no pass over the matrix for the scales
-int i8s_cut_planes(nngp_model* m, I8Planes& pk, const double* kmat, int64_t kld, hipStream_t s) {
-    I8Work& w = m->i8;
-    NNGP_TRY(launch_i8s_diag_bound_scale(kmat, kld, m->np, pk.scale, s));
-    // a bitwise symmetric matrix (one symmetric kernel build; the NNGP kernel beside an NTK fit always is): every entry read once
-    const bool sym = (kmat == m->kaux64 || m->k64_symmetric) && (pk.alloc_planes == 5 || pk.alloc_planes == 7) && NNGP_KNOB(5) != 62;
-    if (sym)
-        NNGP_TRY(launch_i8s_slice_sym(kmat, kld, m->np, pk.alloc_planes, pk.scale, pk.planes, m->np_cap, w.k_rows * m->np_cap, s));
-    else
-        NNGP_TRY(launch_i8s_slice_rows(kmat, kld, m->np, m->np, pk.alloc_planes, pk.scale, nullptr, pk.planes, m->np_cap, w.k_rows * m->np_cap, s));
-    NNGP_TRY(launch_i8s_scale_sqsum(pk.scale, m->np, pk.scale + m->np_cap, s));
-    pk.ns_done = pk.alloc_planes;
-    pk.ready = true;
-    return 0;
-}
-
-// out [mp, np] = beta cin + alpha z Kmat + gamma z on the int8 pipe; Kmat: a symmetric positive semi-definite [np, np] kernel matrix
-// (k64, or kaux64 beside an NTK fit) whose digit planes are kept in pk (workspace: ensure_i8s, by the caller).
-// The planes (13 N^2 bytes of HBM traffic to cut 5 of them: 2.7 ms at N = 32768) are cut once per change of the matrix: by
-// nngp_model_predict on the solve stream beside its first blocked solves (-0.8 ms against stream order at N = 32768), else here in
-// stream order.  Measured and dropped (profiles/r3_i8s_slicing_placement.json): slicing beside the FACTORISATION on a second stream
-// costs the Cholesky exactly what the slicing takes, at any stream priority and wherever in the factorisation it starts -- its 32768
-// small workgroups settle on every compute unit a trailing-update launch has just left and the next launch waits for them -- and on
-// a CU-masked stream (1 / 2 / 4 units per XCD) it needs 95 / 64 / 55 ms: one compute unit moves ~20 GB/s of it.
-int i8s_product_rows(nngp_model* m, I8Planes& pk, const double* kmat, int64_t kld, double* out, const double* cin, double beta,
-                     double alpha, double* z, double gamma, int64_t mp, hipStream_t s, int grade) {
-    const int64_t np = m->np;
-    I8Work& w = m->i8;
-    // COARSE: z comes straight from the float32 solves and every identity downstream holds for WHATEVER z they returned -- so z is
-    // rounded to 24-bit fixed point below its row maximum (three planes; the solves' own error is ~1e-4 of it) and written back:
-    // the planes ARE z, planes 3 and 4 do not exist, 12 plane products instead of 15 and no truncation on the z side
-    // FINE (round 4, late): the same for the later residuals and the NTK's W = Z K_dd with five planes -- 25 products instead of 28 (timing-knob key 5 = 64: seven)
-    const int fine_z = NNGP_KNOB(5) == 64 ? kI8FinePlanes : kI8FineZPlanes;
-    const bool round_z = grade == I8_COARSE ? w.ns_z < w.ns_k : fine_z < kI8FinePlanes;
-    const bool fuse_rows = grade == I8_COARSE && m->i8_fuse_request && cin != nullptr && w.rowpart_rows >= mp && NNGP_KNOB(5) != 59;
-    const int ns_z = grade == I8_FINE ? fine_z : w.ns_z, ns_k = grade == I8_FINE ? kI8FinePlanes : w.ns_k;
-    const int cut = grade == I8_FINE ? kI8FineCut : w.cut;
-    NNGP_REQUIRE(pk.alloc_planes >= ns_k && w.z_planes >= ns_z, "i8s_product_rows: workspace for %d planes missing", ns_k);
-    if (!pk.ready || pk.ns_done < ns_k) {
-        NNGP_TRY(i8s_cut_planes(m, pk, kmat, kld, s));
-    } else if (&pk == &m->i8.k && m->i8_k_pending) {  // cut on the solve stream at the start of this predict
-        NNGP_HIP_CHECK(hipStreamWaitEvent(s, m->ev_i8, 0));
-    }
-    if (&pk == &m->i8.k) m->i8_k_pending = false;
-    I8Plan pl;
-    NNGP_TRY(i8s_plan(ns_z, ns_k, cut, &pl));
-    const int64_t nchunk = i8s_chunks(np, &pl);
-    for (int64_t r0 = 0; r0 < mp; r0 += kI8RowBlock) {
-        const int64_t mb = mp - r0 < kI8RowBlock ? mp - r0 : kI8RowBlock;
-        const int64_t slab = mb * np;
-        NNGP_TRY(launch_i8s_slice_rows(z + r0 * np, np, mb, np, ns_z, nullptr, w.zscale, w.zplanes, m->np_cap, (w.z_rows + 256) * m->np_cap, s,
-                                       round_z ? z + r0 * np : nullptr));
-        if (r0 == 0 && grade == I8_COARSE && !m->gate_recorded && NNGP_KNOB(2) != 8 && NNGP_KNOB(2) != 9 && !cg_from_the_start(m, mp)) {
-            // The deferred alpha CG (solve stream) starts HERE, not with the blocked solves before this product: its hundreds of small
-            // GEMV launches settle on compute units between the solves' persistent split-float16 launches (which need a whole unit's
-            // LDS) and cost them 3.7 ms at N = 32768 (scripts/cov_alone.py); beside this one long launch they fit the wave slots and
-            // the 32 KB of LDS it leaves.
-            if (m->ev_gate == nullptr) NNGP_HIP_CHECK(hipEventCreateWithFlags(&m->ev_gate, hipEventDisableTiming));
-            NNGP_HIP_CHECK(hipEventRecord(m->ev_gate, s));
-            m->gate_recorded = true;
-        }
-        const bool timed = w.timed && w.t_count < I8Work::kMaxTimed;
-        if (timed) {
-            const int t = w.t_count;
-            if (w.t0[t] == nullptr) NNGP_HIP_CHECK(hipEventCreate(&w.t0[t]));
-            if (w.t1[t] == nullptr) NNGP_HIP_CHECK(hipEventCreate(&w.t1[t]));
-            NNGP_HIP_CHECK(hipEventRecord(w.t0[t], s));
-        }
-        NNGP_TRY(launch_gemm_nt_i8s(w.partial, np, slab, w.zplanes, m->np_cap, (w.z_rows + 256) * m->np_cap, pk.planes, m->np_cap,
-                                    w.k_rows * m->np_cap, pl, mb, np, np, w.counters, 0, s));
-        if (timed) {
-            const int t = w.t_count++;
-            NNGP_HIP_CHECK(hipEventRecord(w.t1[t], s));
-            w.t_flops[t] = 2.0 * (double)mb * (double)np * (double)np;
-            w.t_ops[t] = w.t_flops[t] * pl.npairs;
-        }
-        I8Fuse fuse;
-        fuse.out32 = m->b32 + r0 * np;
-        fuse.ld32 = np;
-        fuse.part = w.rowpart + r0 * i8s_col_blocks(np) * 4;
-        NNGP_TRY(launch_i8s_combine(out + r0 * np, np, cin ? cin + r0 * np : nullptr, np, beta, alpha, z + r0 * np, np, gamma, w.partial, np,
-                                    slab, (int)nchunk, pl.ndiag, w.zscale, pk.scale, mb, np, s, fuse_rows ? &fuse : nullptr));
-    }
-    if (fuse_rows) m->i8_fuse_done = true;
-    if (grade == I8_COARSE && !m->gate_recorded && NNGP_KNOB(2) == 9) {  // timing experiment: the CG starts when the product has ended
-        if (m->ev_gate == nullptr) NNGP_HIP_CHECK(hipEventCreateWithFlags(&m->ev_gate, hipEventDisableTiming));
-        NNGP_HIP_CHECK(hipEventRecord(m->ev_gate, s));
-        m->gate_recorded = true;
-    }
-    return 0;
-}
-
-// out [mp, np] = rhs - z (K + reg I) for z = z64 (or another [mp, np] block).
-// first_residual: z comes straight from the float32 solves, so the residual is ~1e-4 of rhs and the COARSE product's error floor
-// (2^-32 sqrt(N) of the row maxima, ~1e-3 of such a residual) is harmless: the NNGP level-1 variance moves by 2e-7 (N = 32768) ..
-// 7e-7 (ill-conditioned sweep case), a first correction sweep loses nothing.  Every LATER residual is ~1e-8 of rhs and needs float64
-// grade proper -- measured with the coarse product there (scripts/i8s_hard_case.py): NTK variances off by 3e-5 .. 2e-4 (first order
-// in the rows' error) against 1e-8, NNGP level 2 at 1e-7 instead of 1e-8, the explicit inverse of the serving mode stuck four digits
-// short of float64 (serving variances 4e-3 off).  Those take the FINE product where it pays, else the float64 pipe.
-int residual_rows(nngp_model* m, double* out, const double* rhs, double* z, int64_t mp, hipStream_t s, bool first_residual) {
-    const int64_t np = m->np;
-    const bool coarse = first_residual;
-    if (!coarse && use_i8s_fine(m, mp)) m->i8_want_fine = true;
-    if (coarse ? use_i8s(m, mp) : use_i8s_fine(m, mp)) {
-        const int rc = ensure_i8s(m, mp, m->i8.k, coarse ? i8s_planes_policy(m) : kI8FinePlanes);
-        if (rc == 0) {
-            if (coarse) m->i8_used_now = true;
-            return i8s_product_rows(m, m->i8.k, m->k64, m->ld, out, rhs, 1.0, -1.0, z, -m->reg, mp, s, coarse ? I8_COARSE : I8_FINE);
-        }
-        if (rc != 1) return rc;  // 1: no room for the planes -- the float64 pipe below
-    }
-    NNGP_TRY(launch_gemm_nt_f64(out, np, rhs, np, z, np, m->k64, m->ld, mp, np, np, -1.0, 1.0, s));
-    return launch_axpby_mat(out, 1.0, z, -m->reg, np, mp, np, s);
-}
-
 // every reader of m->tri calls this on the stream it reads from: builds the inverted blocks there if nobody has yet, else orders the
 // stream behind whoever did
 int tri_join(nngp_model* m, hipStream_t s) {
@@ -419,7 +209,26 @@ bool cg_from_the_start(const nngp_model* m, int64_t mp) { return ticket_schedule
 
 // While the digit planes of K are being cut on the solve stream (one 132 KB workgroup per compute unit: it cannot share a unit with a
 // persistent solve) the solves leave it some units; the alpha CG's light kernels fit beside the solve's workgroups as they are.
-int tickets_reserve(const nngp_model* m) { return m->i8_k_pending ? ticket_schedule().reserve : 0; }
+int tickets_reserve(const nngp_model* m) { return m->i8.k_pending ? ticket_schedule().reserve : 0; }
+
+// The stream of a predict's early plane cut (cut_planes_early): the solve stream -- but with the alpha CG running from the predict's
+// start (cg_from_the_start) the cut must not sit in front of it on the solve stream, nor in front of the inverted blocks on the
+// panel stream
+hipStream_t early_cut_stream(const nngp_model* m, int64_t mp) {
+    const int cut_stream = ticket_schedule().cutstream;
+    hipStream_t cs = m->solve_stream;
+    if (cut_stream != 0 && cg_from_the_start(m, mp) && m->la != nullptr && m->la->panel != nullptr)
+        cs = (cut_stream == 2 && m->la->update != nullptr) ? m->la->update : m->la->panel;
+    return cs;
+}
+
+// From here on `s` the deferred alpha CG (solve stream) may run: run_pending_solve waits for the gate when one was recorded
+int record_cg_gate(nngp_model* m, hipStream_t s) {
+    if (m->ev_gate == nullptr) NNGP_HIP_CHECK(hipEventCreateWithFlags(&m->ev_gate, hipEventDisableTiming));
+    NNGP_HIP_CHECK(hipEventRecord(m->ev_gate, s));
+    m->gate_recorded = true;
+    return 0;
+}
 
 // a persistent solve that gave up waiting left its error word behind: report it once, and keep the model off that path
 int tickets_check(nngp_model* m, bool wait) {
@@ -432,21 +241,8 @@ int tickets_check(nngp_model* m, bool wait) {
 
 // event pair around one blocked solve of mp right-hand sides (np^2 mp flops: a triangular matrix, multiply-add = 2)
 static int trsm_timer_begin(nngp_model* m, int64_t mp, hipStream_t s, int* slot) {
-    auto& t = m->trsm_t;
-    *slot = -1;
-    if (!t.timed || t.count >= nngp_model::TrsmTimer::kMax) return 0;
-    const int i = t.count;
-    if (t.t0[i] == nullptr) NNGP_HIP_CHECK(hipEventCreate(&t.t0[i]));
-    if (t.t1[i] == nullptr) NNGP_HIP_CHECK(hipEventCreate(&t.t1[i]));
-    NNGP_HIP_CHECK(hipEventRecord(t.t0[i], s));
-    t.flops[i] = (double)m->np * (double)m->np * (double)mp;
-    *slot = i;
-    return 0;
-}
-static int trsm_timer_end(nngp_model* m, int slot, hipStream_t s) {
-    if (slot < 0) return 0;
-    NNGP_HIP_CHECK(hipEventRecord(m->trsm_t.t1[slot], s));
-    m->trsm_t.count = slot + 1;
+    NNGP_TRY(m->trsm_t.begin(s, slot));
+    if (*slot >= 0) m->trsm_flops[*slot] = (double)m->np * (double)m->np * (double)mp;
     return 0;
 }
 
@@ -459,7 +255,7 @@ int apply_forward_f32(nngp_model* m, int64_t mp, hipStream_t s) {
     int slot = -1;
     NNGP_TRY(trsm_timer_begin(m, mp, s, &slot));
     NNGP_TRY(apply_forward_untimed(m, mp, s));
-    return trsm_timer_end(m, slot, s);
+    return m->trsm_t.end(slot);
 }
 
 static int apply_forward_untimed(nngp_model* m, int64_t mp, hipStream_t s) {
@@ -489,9 +285,7 @@ int apply_inverse_f32(nngp_model* m, int64_t mp, hipStream_t s) {
     }
     NNGP_TRY(apply_forward_f32(m, mp, s));
     if (NNGP_KNOB(2) == 10 && !m->gate_recorded && m->solve_pending) {  // timing experiment: the deferred alpha CG starts with the backward solve
-        if (m->ev_gate == nullptr) NNGP_HIP_CHECK(hipEventCreateWithFlags(&m->ev_gate, hipEventDisableTiming));
-        NNGP_HIP_CHECK(hipEventRecord(m->ev_gate, s));
-        m->gate_recorded = true;
+        NNGP_TRY(record_cg_gate(m, s));
     }
     if (lt_aside) NNGP_HIP_CHECK(hipStreamWaitEvent(s, m->ev_lt, 0));
     // (whoever gets here on the float32 path finds its operand built: round 4's null-pointer abort came from a caller that had not)
@@ -507,7 +301,7 @@ int apply_inverse_f32(nngp_model* m, int64_t mp, hipStream_t s) {
         NNGP_TRY(trsm_rut_blocks_h3(m->b32, m->np, mp, m->lt_ready ? m->lt32 : nullptr, m->np, m->tri, m->np, m->trsm_tmp, m->split, s));
     else
         NNGP_TRY(trsm_rut_blocks_f32(m->b32, m->np, mp, m->lt32, m->np, m->tri, m->np, m->trsm_tmp, s));
-    return trsm_timer_end(m, slot, s);
+    return m->trsm_t.end(slot);
 }
 
 // NTK covariance: the error of Z enters in first order (no cancellation as in the NNGP form), so what the sweeps leave is
@@ -521,15 +315,16 @@ static int ntk_sweeps(const nngp_model* m) { return m->var_refine < 2 ? 2 : m->v
 // final_residual: also leave r64 = rhs - z64 (K + reg I) for the returned z64 (one more float64 product).
 // measure (sweeps >= 2): the error energies r . M^-1 r that the first two corrections saw are kept in rows.var and
 // rows.delta, and z . rhs in rows.tol, for k_sweep_estimate -- three passes over [mp, np].
+// note (optional): handed to every residual (ResidualNote).
 int refined_solve_rows(nngp_model* m, const double* rhs, int64_t mp, int sweeps, bool final_residual, hipStream_t s,
-                       bool measure) {
+                       bool measure, ResidualNote* note) {
     const int64_t np = m->np;
     measure = measure && sweeps >= 2;
     NNGP_TRY(launch_convert_f64_f32(rhs, np, m->b32, np, mp, np, mp, np, s));
     NNGP_TRY(apply_inverse_f32(m, mp, s));
     NNGP_TRY(launch_f32_to_f64_mat(m->b32, np, m->z64, np, mp, np, false, s));
     for (int it = 0; it < sweeps + (final_residual ? 1 : 0); ++it) {
-        NNGP_TRY(residual_rows(m, m->r64, rhs, m->z64, mp, s, it == 0));
+        NNGP_TRY(residual_rows(m, m->r64, rhs, m->z64, mp, s, it == 0, note));
         if (it == sweeps) break;
         NNGP_TRY(launch_convert_f64_f32(m->r64, np, m->b32, np, mp, np, mp, np, s));
         NNGP_TRY(apply_inverse_f32(m, mp, s));
@@ -601,33 +396,7 @@ static int continuation_budget(const nngp_model* m) {
     return (int)fmin(1000.0, 80.0 * shift);
 }
 
-// ---- nngp_model_predict: what one call knows and finds out, and its stages in the order predict_impl runs them ----
-
-// What the covariance leaves to be checked afterwards: were its fixed correction sweeps enough?  (levels >= 1; preconditioner_is_weak)
-enum class CovCheck {
-    None,            // nothing to check
-    NngpDiag,        // NNGP variances by the second-order formula
-    NngpFull,        // NNGP full covariance by the second-order formula: r64 holds G = K_td + R
-    Ntk,             // NTK, variances or full
-    NngpDiagLevel1,  // NNGP variances at level 1: like NngpDiag, and r64 already holds the residual of z64
-};
-
-struct PredictCall {
-    hipStream_t s = nullptr;
-    const double* xt = nullptr;        // the query rows (x_test = None: the training rows)
-    const double* qt = nullptr;        // their |x|^2 / d
-    const double* ktd = nullptr;       // cross kernel of `get`, [mp, np] (x_test = None: K_td = K_dd (estimator.py:37-40); its padding is zero)
-    const double* ktd_nngp = nullptr;  // NTK covariance: the NNGP cross kernel
-    int64_t mt = 0, mp = 0;
-    bool on_train = false, is_ntk = false, want_cov = false, full = false;
-    bool compact_train = false;  // x_test = None and K_dd's rows have stride ld != np: they are copied to the compact cross buffer
-    bool serving = false;        // Z = K_td X with the explicit float64 inverse: one product, no solves
-    double *mean = nullptr, *var_or_cov = nullptr;
-    // what the covariance stage found out
-    bool z_valid = false;           // z64 ends up holding the rows K_td (K + reg I)^-1 (to first order): the mean can be corrected through them
-    bool i8_check_pending = false;  // first level-1 predict of a fit on the int8 residual: it waits for its own guard estimate
-    CovCheck check = CovCheck::None;
-};
+// ---- nngp_model_predict: its stages in the order predict_impl runs them (what one call knows and finds out: PredictCall, model.h) ----
 
 // Row flag: a LOWER bound of the remaining relative variance error above this value (debug key 6 = e >= 2: 10^-e).
 // The bound is loose -- measured 1e-10 where the error is 4e-7 (N = 32768, scripts/flag_study.py) -- so it is only the
@@ -663,33 +432,6 @@ static int predict_open(nngp_model* m, const double* x_test, int64_t mt, int32_t
     return ensure_predict_capacity(m, mt, !c.on_train || c.compact_train);
 }
 
-// Stage 2.  A predict whose covariance will take the int8 residual product right after a fit: the digit planes of K (13 N^2 bytes of HBM
-// traffic, 2.7 ms alone at N = 32768) are cut beside the predict's first kernels.  The cut's workgroups hold 132 KB of LDS and cannot
-// share a compute unit with a workgroup of the persistent solves, so what is left of it when the first solve starts waits for the
-// gaps between and behind the solves: it is enqueued FIRST (round 5: before the cross kernel and the inverted blocks, on the
-// look-ahead's idle update stream -- it needs nothing but K) and has the chip until then.  (debug key 5 = 53: in stream order
-// where the planes are first needed)
-static int cut_planes_early(nngp_model* m, PredictCall& c) {
-    if (!(c.want_cov && m->var_refine >= 1 && use_i8s(m, c.mp) && !c.serving && NNGP_KNOB(5) != 53)) return 0;
-    if (c.full && use_i8s_fine(m, c.mp)) m->i8_want_fine = true;  // a full covariance runs at level >= 2: later residuals
-    const int rc_i8 = ensure_i8s(m, c.mp, m->i8.k, i8s_planes_policy(m));
-    if (rc_i8 != 0 && rc_i8 != 1) return rc_i8;
-    if (rc_i8 != 0 || m->i8.k.ready) return 0;
-    if (m->ev_i8 == nullptr) NNGP_HIP_CHECK(hipEventCreateWithFlags(&m->ev_i8, hipEventDisableTiming));
-    NNGP_HIP_CHECK(hipEventRecord(m->ev_i8, c.s));  // K is complete; earlier readers of the planes are behind us
-    // With the alpha CG running from the predict's start (cg_from_the_start) the cut must not sit in front of it on the solve
-    // stream, nor in front of the inverted blocks on the panel stream
-    const int cut_stream = ticket_schedule().cutstream;
-    hipStream_t cs = m->solve_stream;
-    if (cut_stream != 0 && cg_from_the_start(m, c.mp) && m->la != nullptr && m->la->panel != nullptr)
-        cs = (cut_stream == 2 && m->la->update != nullptr) ? m->la->update : m->la->panel;
-    NNGP_HIP_CHECK(hipStreamWaitEvent(cs, m->ev_i8, 0));
-    NNGP_TRY(i8s_cut_planes(m, m->i8.k, m->k64, m->ld, cs));
-    NNGP_HIP_CHECK(hipEventRecord(m->ev_i8, cs));
-    m->i8_k_pending = true;
-    return 0;
-}
-
 // Stage 4: the cross kernel of `get` (the mean is mu = K_td alpha, float64), or the compact copy of K_dd for x_test = None
 static int build_cross_kernel(nngp_model* m, PredictCall& c) {
     const int64_t np = m->np;
@@ -708,16 +450,6 @@ static int build_cross_kernel(nngp_model* m, PredictCall& c) {
     return 0;
 }
 
-// Stage 5: the previous level-1 batch's guard estimate, if it has arrived (record_i8_guard_estimate sent it on its way)
-static void take_in_guard_word(nngp_model* m) {
-    if (!(m->i8_guard_pending && hipEventQuery(m->ev_guard) == hipSuccess)) return;
-    double ratio = 0.0;
-    memcpy(&ratio, m->i8_guard_host, sizeof(double));
-    m->i8_guard_pending = false;
-    if (ratio > m->i8_floor_ratio) m->i8_floor_ratio = ratio;
-    if (!(ratio <= (NNGP_KNOB(5) == 56 ? 0.0 : kI8FloorThr))) m->i8_distrusted = true;  // float64 pipe from this predict on (key 5 = 56: test)
-}
-
 // ---- stage 6: the covariance, one function per case (form_covariance chooses) ----
 
 static int build_ktt(nngp_model* m, const PredictCall& c) {  // NNGP K_tt [mt, mt] into ktt64 (ld = mp)
@@ -731,15 +463,15 @@ static int build_ktt(nngp_model* m, const PredictCall& c) {  // NNGP K_tt [mt, m
 // one product with the explicit inverse.  Either way z64 only has to be GOOD, not exact: the second-order formulas
 // of the callers square its error.  (K_td X alone would not do: k^T X k cancels to the variance from terms 1e3..1e6 larger,
 // and no float64 inverse is accurate to that.)
-static int solve_cross_rows(nngp_model* m, const PredictCall& c, int sweeps, bool final_residual) {
+static int solve_cross_rows(nngp_model* m, const PredictCall& c, int sweeps, bool final_residual, ResidualNote* note = nullptr) {
     const int64_t np = m->np;
-    if (!c.serving) return refined_solve_rows(m, c.ktd, c.mp, sweeps, final_residual, c.s);
+    if (!c.serving) return refined_solve_rows(m, c.ktd, c.mp, sweeps, final_residual, c.s, false, note);
     NNGP_TRY(launch_gemm_nt_f64(m->z64, np, nullptr, 0, c.ktd, np, m->ainv64, np, c.mp, np, np, 1.0, 0.0, c.s));
     if (m->serving_weak) {  // ill-conditioned fit: X is less accurate; one correction step with X as the solver
-        NNGP_TRY(residual_rows(m, m->r64, c.ktd, m->z64, c.mp, c.s, false));
+        NNGP_TRY(residual_rows(m, m->r64, c.ktd, m->z64, c.mp, c.s, false, note));
         NNGP_TRY(launch_gemm_nt_f64(m->z64, np, m->z64, np, m->r64, np, m->ainv64, np, c.mp, np, np, 1.0, 1.0, c.s));
     }
-    if (final_residual) NNGP_TRY(residual_rows(m, m->r64, c.ktd, m->z64, c.mp, c.s, false));
+    if (final_residual) NNGP_TRY(residual_rows(m, m->r64, c.ktd, m->z64, c.mp, c.s, false, note));
     return 0;
 }
 
@@ -754,29 +486,6 @@ static int cov_float32_only(nngp_model* m, PredictCall& c) {
     return launch_cov_finish(m->ktt64, mp, m->vvt32, mp, mt, c.var_or_cov, c.s);
 }
 
-// An int8 residual went into a level-1 batch: what may the dropped digit pairs have cost THIS batch's variances?  The estimate's one
-// word waits for the first predict's verdict (first_guard_verdict), or travels to the host for the NEXT predict (take_in_guard_word).
-static int record_i8_guard_estimate(nngp_model* m, PredictCall& c) {
-    I8Plan pl;
-    NNGP_TRY(i8s_plan(m->i8.ns_z, m->i8.ns_k, m->i8.cut, &pl));
-    if (m->i8_guard == nullptr) {
-        NNGP_TRY(dev_alloc(&m->i8_guard, 1));
-        NNGP_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&m->i8_guard_host), sizeof(unsigned long long), hipHostMallocDefault));
-    }
-    if (m->ev_guard == nullptr) NNGP_HIP_CHECK(hipEventCreateWithFlags(&m->ev_guard, hipEventDisableTiming));
-    NNGP_HIP_CHECK(hipMemsetAsync(m->i8_guard, 0, sizeof(unsigned long long), c.s));
-    NNGP_TRY(launch_i8s_floor_ratio_rows(m->rows.zstat, c.mt, c.var_or_cov, pl, m->i8.ns_z, m->i8.ns_k, m->i8.k.scale + m->np_cap,
-                                         m->i8_guard, c.s));
-    if (!m->i8_checked) {
-        c.i8_check_pending = true;   // first predict of the fit: waits for its own estimate (first_guard_verdict)
-    } else {
-        NNGP_HIP_CHECK(hipMemcpyAsync(m->i8_guard_host, m->i8_guard, sizeof(unsigned long long), hipMemcpyDeviceToHost, c.s));
-        NNGP_HIP_CHECK(hipEventRecord(m->ev_guard, c.s));
-        m->i8_guard_pending = true;  // looked at when the next predict starts
-    }
-    return 0;
-}
-
 // NNGP diag at level 1: ONE float64 product and three triangular solves (the default).  With z0 = M^-1 k from the float32 factor
 // M = L L^T and r0 = k - A z0:   k^T A^-1 k = z0.(k + r0) + e0^T A e0   exactly, for whatever z0 the solves
 // returned, and   e0^T A e0 = r0^T A^-1 r0 ~ r0^T M^-1 r0 = |L^-1 r0|^2   -- a forward solve only, and only the
@@ -786,24 +495,23 @@ static int record_i8_guard_estimate(nngp_model* m, PredictCall& c) {
 // (an int8 residual's combination pass also leaves z.(k + r0), z.r0, the statistics of z and float32(r0): I8Fuse)
 static int cov_nngp_diag_level1(nngp_model* m, PredictCall& c) {
     const int64_t np = m->np, mt = c.mt, mp = c.mp;
-    m->i8_fuse_done = false;
-    {
-        ScopedFlag fuse(m->i8_fuse_request);
-        NNGP_TRY(solve_cross_rows(m, c, 0, true));
-    }
+    ResidualNote note;
+    note.want_fused_rows = true;
+    NNGP_TRY(solve_cross_rows(m, c, 0, true, &note));
+    if (note.used_int8) c.used_i8 = true;
     c.z_valid = true;
-    if (m->i8_fuse_done) {
-        NNGP_TRY(launch_i8s_rowstat_finish(m->i8.rowpart, np, mt, m->tt_diag, c.var_or_cov, m->rows.delta, m->rows.zstat, c.s));
+    if (note.fused) {
+        NNGP_TRY(launch_i8s_rowstat_finish(m->i8.work.rowpart, np, mt, m->tt_diag, c.var_or_cov, m->rows.delta, m->rows.zstat, c.s));
     } else {
         NNGP_TRY(launch_rowdot_f64(m->z64, c.ktd, 1.0, m->r64, np, mt, np, m->tt_diag, -1.0, c.var_or_cov, c.s));
         NNGP_TRY(launch_rowdot_f64(m->z64, nullptr, 0.0, m->r64, np, mt, np, nullptr, 1.0, m->rows.delta, c.s,
-                                   m->i8_used_now ? m->rows.zstat : nullptr));
+                                   c.used_i8 ? m->rows.zstat : nullptr));
         NNGP_TRY(launch_convert_f64_f32(m->r64, np, m->b32, np, mp, np, mp, np, c.s));
     }
     NNGP_TRY(apply_forward_f32(m, mp, c.s));
     NNGP_TRY(launch_row_sqsum_f32(m->b32, np, mt, np, c.var_or_cov, c.var_or_cov, c.s));
     c.check = CovCheck::NngpDiagLevel1;
-    if (m->i8_used_now) NNGP_TRY(record_i8_guard_estimate(m, c));
+    if (c.used_i8) NNGP_TRY(record_i8_guard_estimate(m, c));
     return launch_rows_prepare(m->rows.delta, m->tt_diag, c.var_or_cov, nullptr, 0, row_flag_threshold(), mt, m->rows.tol,
                                m->rows.live + 1, c.s);
 }
@@ -881,14 +589,7 @@ static int cov_nngp_general(nngp_model* m, PredictCall& c, int level) {
 // NTK: the covariance from z64 = Theta_td (Theta_dd + reg I)^-1; K_tt already in ktt64 (full).  Runs again after a continuation.
 static int ntk_finish(nngp_model* m, const PredictCall& c) {
     const int64_t np = m->np, mt = c.mt, mp = c.mp;
-    // W = Z K_dd: its error is the variance's -- float64 grade proper (the FINE product where it pays)
-    int rc_w = use_i8s_fine(m, mp) ? ensure_i8s(m, mp, m->i8.aux, kI8FinePlanes) : 1;
-    if (rc_w == 0) {
-        NNGP_TRY(i8s_product_rows(m, m->i8.aux, m->kaux64, np, m->r64, nullptr, 0.0, 1.0, m->z64, 0.0, mp, c.s, I8_FINE));
-    } else {
-        if (rc_w != 1) return rc_w;
-        NNGP_TRY(launch_gemm_nt_f64(m->r64, np, nullptr, 0, m->z64, np, m->kaux64, np, mp, np, np, 1.0, 0.0, c.s));
-    }
+    NNGP_TRY(kaux_product_rows(m, m->r64, m->z64, mp, c.s));  // W = Z K_dd
     if (!c.full)  // var_i = K_tt,ii + z_i . (w_i - 2 k_i)
         return launch_rowdot_f64(m->z64, c.ktd_nngp, -2.0, m->r64, np, mt, np, m->tt_diag, 1.0, c.var_or_cov, c.s);
     NNGP_TRY(launch_axpby_mat(m->r64, 1.0, c.ktd_nngp, -1.0, np, mp, np, c.s));  // G = W - K_td
@@ -913,7 +614,7 @@ static int cov_ntk(nngp_model* m, PredictCall& c) {
         NNGP_TRY(launch_kernel_build(a, m->arch, c.s));
         NNGP_TRY(launch_zero_pad_f64(m->kaux64, np, n, np, c.s));
         m->aux_ready = true;
-        m->i8.aux.ready = false;
+        m->i8.work.aux.ready = false;
     }
     const double* ktd_n = m->kaux64;  // NNGP cross kernel; x_test=None: K_dd itself
     if (!c.on_train) {
@@ -961,23 +662,6 @@ static int form_covariance(nngp_model* m, PredictCall& c) {
     if (!c.full && c.serving && c.mt <= (m->np <= 16384 ? 32 : 16) && !m->serving_weak) return cov_nngp_diag_few_queries(m, c);
     if (!c.full && level >= 2) return cov_nngp_diag_second_order(m, c, level);
     return cov_nngp_general(m, c, level);
-}
-
-// Stage 8: the first level-1 predict of a fit on the int8 residual waits for its own guard estimate; distrusted, the covariance is
-// formed again on the float64 pipe, where the fit stays.
-// (the host has just waited for the alpha solve: this read-back waits for the covariance kernels enqueued before it, once
-// per fit -- later predicts on the fit stay asynchronous)
-static int first_guard_verdict(nngp_model* m, PredictCall& c) {
-    if (!c.i8_check_pending) return 0;
-    NNGP_HIP_CHECK(hipMemcpyAsync(m->i8_guard_host, m->i8_guard, sizeof(unsigned long long), hipMemcpyDeviceToHost, c.s));
-    NNGP_HIP_CHECK(hipStreamSynchronize(c.s));
-    memcpy(&m->i8_floor_ratio, m->i8_guard_host, sizeof(double));
-    m->i8_checked = true;
-    const double thr = NNGP_KNOB(5) == 56 ? 0.0 : kI8FloorThr;  // key 5 = 56: distrust whatever the estimate says (test)
-    if (m->i8_floor_ratio <= thr) return 0;
-    m->i8_distrusted = true;  // use_i8s is false from here on: the covariance again, on the float64 pipe
-    m->i8_used_now = false;
-    return form_covariance(m, c);
 }
 
 // Stage 9.  Were the fixed sweeps enough?  Two signs that the float32 factor is a weak preconditioner: the alpha solve needed
@@ -1087,7 +771,7 @@ int nngp_model_prepare_serving(nngp_model* m, void* stream) {
     // sweeps four digits short of it -- measured: 4e-3 in the serving variances at N = 2500 against 1e-7 (scripts/i8s_hard_case.py).
     // Nor the FINE product: an inverse refined against it serves variances at 1e-9 .. 6e-9 of level 3 where the float64 pipe's
     // reaches 2e-11 .. 5e-11, for 10-20 % of the build time (scripts/i8s_serving_build.py).
-    ScopedFlag suspend(m->i8_suspended);
+    ScopedFlag suspend(m->i8.suspended);
     for (int64_t r0 = 0; r0 < n; r0 += blk) {
         const int64_t rows = (n - r0 < blk) ? n - r0 : blk, rp = round_up(rows, TB);
         NNGP_TRY(launch_identity_rows(m->ktd64, np, np, r0, rows, rp, s));
@@ -1107,7 +791,8 @@ int nngp_model_prepare_serving(nngp_model* m, void* stream) {
     return 0;
 }
 
-// The posterior of one batch of queries, stage by stage (the stages: above, in this order)
+// The posterior of one batch of queries, stage by stage (the stages: above, in this order; 2, 5 and 8 -- the int8 residual's early
+// plane cut and its guard -- in residual_i8.hip)
 static int predict_impl(nngp_model* m, const double* x_test, int64_t mt, int32_t cov_mode, double* mean, double* var_or_cov,
                         void* stream) {
     PredictCall c;
@@ -1117,11 +802,13 @@ static int predict_impl(nngp_model* m, const double* x_test, int64_t mt, int32_t
     NNGP_TRY(tri_fork(m, c.s));  // first predict of a fit: the factor's inverted blocks are built beside the cross-kernel build
     NNGP_TRY(build_cross_kernel(m, c));
     take_in_guard_word(m);
-    m->i8_used_now = false;
+    c.used_i8 = false;
     m->gate_recorded = false;
     if (c.want_cov) NNGP_TRY(form_covariance(m, c));
     NNGP_TRY(run_pending_solve(m, c.s, true, c.z_valid));
-    NNGP_TRY(first_guard_verdict(m, c));
+    bool redo_cov = false;
+    NNGP_TRY(first_guard_verdict(m, c, &redo_cov));
+    if (redo_cov) NNGP_TRY(form_covariance(m, c));  // the int8 guard distrusts the first result
     m->cov_iters = 0;
     m->sweep_est = m->sweep_est_var = -1.0;
     if (c.check != CovCheck::None && NNGP_KNOB(6) != 1) {

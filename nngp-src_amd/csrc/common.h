@@ -41,7 +41,7 @@ void note_alloc();  // counts a device allocation (nngp_alloc_count)
 //   7  1 = 128-wide recursion in the posterior solves; any non-zero value = float32 solve path; 3 = CG solve in stream
 //      order instead of deferred
 //   5  (also) 1 = old level-1 variance formula (full float64 residual + preconditioned remainder)
-//   5  (also) 50..57 int8 residual path (api.hip: use_i8s, ensure_i8s); round 4: 58 = five digit planes of z instead of three rounded ones;
+//   5  (also) 50..57 int8 residual path (residual_i8.hip: use_i8s, ensure_i8s); round 4: 58 = five digit planes of z instead of three rounded ones;
 //      59 = row statistics and float32 copy in passes of their own instead of the fused combination; 60 = K chunks of 16384 always;
 //      61 = the factor's inverted blocks built in line (not beside the first predict's cross-kernel build); 62 = digit planes of K row by row; 63 = per-layer ReLU recursion in the kernel build (no composite map); 64 = seven z planes in FINE products; 65 = an NTK model's NNGP kernel always in a build of its own
 //   0  (also) 32 = alpha CG runs in stream order inside nngp_model_solve, early-stopped (resumed by whoever needs alpha itself)
@@ -310,11 +310,8 @@ struct I8Work {       // one per model (api.hip): planes of K (and of the NNGP k
     int64_t rowpart_rows = 0;
     int* counters = nullptr;     // work counters of the persistent grid
     int ns_k = 5, ns_z = 5, cut = 4;
-    // live timing of the plane-product launches since the timer was last read (nngp_model_residual_timer_read)
+    // live timing of the plane-product launches since the timer was last read (nngp_model_residual_timer_read): what each timed launch did
     static constexpr int kMaxTimed = 64;
-    bool timed = false;
-    hipEvent_t t0[kMaxTimed] = {}, t1[kMaxTimed] = {};
-    int t_count = 0;
     double t_ops[kMaxTimed] = {};   // executed int8 multiply-adds x 2
     double t_flops[kMaxTimed] = {}; // algorithmic: the float64 product they stand for, 2 m n k
 };

@@ -1,4 +1,4 @@
-// Internal to the C-ABI layer (api.hip, api_predict.hip, api_ops.hip): the model object that owns the device buffers of one GP fit, and the
+// Internal to the C-ABI layer (api.hip, api_predict.hip, residual_i8.hip, api_ops.hip): the model object that owns the device buffers of one GP fit, and the
 // helpers the entry points share.  Not installed; include/nngp_hip.h is the interface.
 #pragma once
 #include <stdarg.h>
@@ -7,6 +7,7 @@
 #include <new>
 #include <mutex>
 #include "common.h"
+#include "i8_trust.h"
 #include <atomic>
 
 namespace nngp {
@@ -38,9 +39,86 @@ inline bool soft_alloc(T** p, int64_t count) {  // false (and no sticky error) w
     return false;
 }
 
-// Estimated |z . dr| / variance above which a fit is taken off the int8 residual: level 1 is itself 1e-6 .. 5e-6 from the converged
-// variance; the bench fits sit at ~1e-7 (nngp_model_residual_floor)
-constexpr double kI8FloorThr = 1e-5;
+// Live timing of up to N launches since it was last read: one event pair around each, created when first used.  Its users keep what
+// each timed launch did (flops, ops) in arrays of their own, by slot.
+template <int N>
+struct EventPairTimer {
+    static constexpr int kMax = N;
+    bool timed = false;
+    int count = 0;
+    hipEvent_t t0[N] = {}, t1[N] = {};
+    hipStream_t stream = nullptr;  // of the pair that is open
+
+    void enable(bool on) { timed = on; count = 0; }
+    int begin(hipStream_t s, int* slot) {  // *slot = -1: off, or full
+        *slot = -1;
+        if (!timed || count >= N) return 0;
+        const int i = count;
+        if (t0[i] == nullptr) NNGP_HIP_CHECK(hipEventCreate(&t0[i]));
+        if (t1[i] == nullptr) NNGP_HIP_CHECK(hipEventCreate(&t1[i]));
+        NNGP_HIP_CHECK(hipEventRecord(t0[i], s));
+        stream = s;
+        *slot = i;
+        return 0;
+    }
+    int end(int slot) {
+        if (slot < 0) return 0;
+        NNGP_HIP_CHECK(hipEventRecord(t1[slot], stream));
+        count = slot + 1;
+        return 0;
+    }
+    int read(double* ms_total) {  // waits for every pair; the caller sums its own arrays over `count` slots, then enable()s or resets count
+        double ms = 0.0;
+        for (int t = 0; t < count; ++t) {
+            NNGP_HIP_CHECK(hipEventSynchronize(t1[t]));
+            float e = 0.0f;
+            NNGP_HIP_CHECK(hipEventElapsedTime(&e, t0[t], t1[t]));
+            ms += e;
+        }
+        *ms_total = ms;
+        return 0;
+    }
+    EventPairTimer() = default;
+    EventPairTimer(const EventPairTimer&) = delete;
+    ~EventPairTimer() {
+        for (int t = 0; t < N; ++t) { if (t0[t]) (void)hipEventDestroy(t0[t]); if (t1[t]) (void)hipEventDestroy(t1[t]); }
+    }
+};
+
+// The float64-grade residual product on the int8 matrix pipe (residual_i8.hip): everything the path keeps per model.
+struct I8Residual {
+    // Sliced int8 copies of K for the residual products of the covariance (gemm_i8s.hip): allocated and cut by the first predict
+    // that takes that path, cut again after every change of K.
+    I8Work work{};
+    EventPairTimer<I8Work::kMaxTimed> timer;  // around the plane products (nngp_model_residual_timer)
+    hipEvent_t ev_i8 = nullptr;  // the planes of K were cut on the solve stream (beside the first blocked solves of a predict)
+    bool k_pending = false;      // ... and the consumer has not waited for that yet
+    bool unavailable = false;    // no room for its workspace on this device: float64 pipe from then on
+    // Guard of the int8 residual (once per fit, on the first predict that used it for a level-1 variance): estimate of what the dropped
+    // digit pairs may have cost the variances, relative to them (k_i8s_floor_ratio); above kI8FloorThr the predict is redone on the
+    // float64 pipe and the fit stays there.
+    // ... and on EVERY later level-1 predict of the fit (round 4: a later batch may sit closer to training points, its variances orders
+    // of magnitude smaller): the estimate comes from statistics the variance's own row-dot pass collects, its one word travels to the host
+    // without a wait and is looked at when the NEXT predict starts -- a batch that trips it sends the fit to the float64 pipe from then on
+    // (the batch itself is not redone: only the first predict of a fit waits for its own estimate).
+    I8Trust trust{};
+    unsigned long long* guard = nullptr;       // device word
+    unsigned long long* guard_host = nullptr;  // pinned
+    hipEvent_t ev_guard = nullptr;
+    bool want_fine = false;   // sticky: see i8s_planes_policy
+    bool suspended = false;   // prepare_serving: the explicit inverse is refined against residuals of the float64 pipe itself
+
+    I8Residual() = default;
+    I8Residual(const I8Residual&) = delete;
+    ~I8Residual() {
+        dev_free(work.k.planes); dev_free(work.k.scale); dev_free(work.aux.planes); dev_free(work.aux.scale); dev_free(work.zplanes);
+        dev_free(work.zscale); dev_free(work.partial); dev_free(work.rowpart); dev_free(work.counters);
+        dev_free(guard);
+        if (guard_host) (void)hipHostFree(guard_host);
+        if (ev_guard) (void)hipEventDestroy(ev_guard);
+        if (ev_i8) (void)hipEventDestroy(ev_i8);
+    }
+};
 }  // namespace nngp
 
 using namespace nngp;
@@ -117,30 +195,9 @@ struct nngp_model {
     double* ktd_aux = nullptr;   // [ktd rows, np_cap] NNGP cross kernel when get == ntk
     int64_t ktd_aux_cap = 0;
 
-    // Sliced int8 copies of K for the residual products of the covariance (gemm_i8s.hip): allocated and cut by the first predict
-    // that takes that path, cut again after every change of K.
-    I8Work i8{};
+    I8Residual i8;  // the covariance's residual products on the int8 matrix pipe (residual_i8.hip)
     hipEvent_t ev_gate = nullptr;  // start of the covariance's int8 plane products on the caller's stream: the deferred alpha CG waits for it
-    bool gate_recorded = false;
-    hipEvent_t ev_i8 = nullptr;  // the planes of K were cut on the solve stream (beside the first blocked solves of a predict)
-    bool i8_k_pending = false;   // ... and the consumer has not waited for that yet
-    bool i8_unavailable = false; // no room for its workspace on this device: float64 pipe from then on
-    // Guard of the int8 residual (once per fit, on the first predict that used it for a level-1 variance): estimate of what the dropped
-    // digit pairs may have cost the variances, relative to them (k_i8s_floor_ratio); above kI8FloorThr the predict is redone on the
-    // float64 pipe and the fit stays there.
-    bool i8_checked = false, i8_distrusted = false, i8_used_now = false;
-    double i8_floor_ratio = -1.0;
-    // ... and on EVERY later level-1 predict of the fit (round 4: a later batch may sit closer to training points, its variances orders
-    // of magnitude smaller): the estimate comes from statistics the variance's own row-dot pass collects, its one word travels to the host
-    // without a wait and is looked at when the NEXT predict starts -- a batch that trips it sends the fit to the float64 pipe from then on
-    // (the batch itself is not redone: only the first predict of a fit waits for its own estimate).
-    unsigned long long* i8_guard = nullptr;       // device word
-    unsigned long long* i8_guard_host = nullptr;  // pinned
-    hipEvent_t ev_guard = nullptr;
-    bool i8_guard_pending = false;
-    bool i8_want_fine = false;  // sticky: see i8s_planes_policy
-    bool i8_fuse_request = false, i8_fuse_done = false;  // level-1 variance: row statistics + float32 copy from the combination pass (I8Fuse)
-    bool i8_suspended = false;   // prepare_serving: the explicit inverse is refined against residuals of the float64 pipe itself  // prepare_serving: the explicit inverse is refined against float64 residuals proper
+    bool gate_recorded = false;    // (record_cg_gate)
 
     double reg = 0.0, trace_mean = 0.0, relres = 0.0;
     // Diagonal shift of the float32 factor's input.  = reg, unless the float32 factorisation of K + reg I broke down
@@ -158,13 +215,8 @@ struct nngp_model {
     // order.  tri_join() is the one gate: every reader of `tri` passes it on the stream it reads from.
     bool tri_stale = false, tri_pending = false;
     // live timing of the posterior's blocked triangular solves (nngp_model_trsm_timer): one event pair per forward / backward solve
-    struct TrsmTimer {
-        static constexpr int kMax = 32;
-        bool timed = false;
-        int count = 0;
-        hipEvent_t t0[kMax] = {}, t1[kMax] = {};
-        double flops[kMax] = {};
-    } trsm_t;
+    EventPairTimer<32> trsm_t;
+    double trsm_flops[decltype(trsm_t)::kMax] = {};  // np^2 mp per timed solve
     hipEvent_t ev_tri = nullptr, ev_tri_fork = nullptr;
     hipEvent_t ev_ready = nullptr, ev_solved = nullptr;
     hipEvent_t ev_lt = nullptr;  // orders the split copy of L^T written on solve_stream (apply_inverse_f32)
@@ -195,14 +247,10 @@ struct nngp_model {
         if (ev_ready) (void)hipEventDestroy(ev_ready);
         if (ev_lt) (void)hipEventDestroy(ev_lt);
         if (ev_tri) (void)hipEventDestroy(ev_tri);
-        for (int t = 0; t < TrsmTimer::kMax; ++t) { if (trsm_t.t0[t]) (void)hipEventDestroy(trsm_t.t0[t]); if (trsm_t.t1[t]) (void)hipEventDestroy(trsm_t.t1[t]); }
         if (ev_tri_fork) (void)hipEventDestroy(ev_tri_fork);
         if (ev_solved) (void)hipEventDestroy(ev_solved);
         if (ev_predict) (void)hipEventDestroy(ev_predict);
-        if (ev_i8) (void)hipEventDestroy(ev_i8);
         if (ev_gate) (void)hipEventDestroy(ev_gate);
-        dev_free(i8.k.planes); dev_free(i8.k.scale); dev_free(i8.aux.planes); dev_free(i8.aux.scale); dev_free(i8.zplanes);
-        for (int t = 0; t < I8Work::kMaxTimed; ++t) { if (i8.t0[t]) (void)hipEventDestroy(i8.t0[t]); if (i8.t1[t]) (void)hipEventDestroy(i8.t1[t]); } dev_free(i8.zscale); dev_free(i8.partial); dev_free(i8.rowpart); dev_free(i8.counters);
         dev_free(split.planes); dev_free(split.counters); dev_free(split.planes_t); dev_free(split.planes_b); dev_free(split.row_inv);
         dev_free(split.ldiag); dev_free(split.dfrag); dev_free(split.dscale);
         tk_destroy(tk);
@@ -210,15 +258,49 @@ struct nngp_model {
         dev_free(lt32); dev_free(dinvt); dev_free(z64); dev_free(r64); dev_free(covp64); dev_free(kaux64); dev_free(ktd_aux);
         dev_free(ainv64);
         dev_free(rows.p); dev_free(rows.q); dev_free(rows.rho); dev_free(rows.coef); dev_free(rows.tol); dev_free(rows.delta);
-        dev_free(rows.var); dev_free(rows.state); dev_free(rows.live); dev_free(rows.zstat); dev_free(i8_guard);
-        if (i8_guard_host) (void)hipHostFree(i8_guard_host);
-        if (ev_guard) (void)hipEventDestroy(ev_guard);
+        dev_free(rows.var); dev_free(rows.state); dev_free(rows.live); dev_free(rows.zstat);
         if (rows.host) (void)hipHostFree(rows.host);
     }
 };
 
 
 namespace nngp {
+// What a caller asks of a residual (residual_rows; refined_solve_rows and solve_cross_rows hand it through) and what it learns.
+struct ResidualNote {
+    bool want_fused_rows = false;  // in: level-1 variance -- row statistics + float32 copy from the int8 combination pass (I8Fuse)
+    bool fused = false;            // out: ... and they were delivered
+    bool used_int8 = false;        // out: a first residual took the int8 pipe
+};
+
+// ---- nngp_model_predict: what one call knows and finds out (its stages: api_predict.hip, in the order predict_impl runs them) ----
+
+// What the covariance leaves to be checked afterwards: were its fixed correction sweeps enough?  (levels >= 1; preconditioner_is_weak)
+enum class CovCheck {
+    None,            // nothing to check
+    NngpDiag,        // NNGP variances by the second-order formula
+    NngpFull,        // NNGP full covariance by the second-order formula: r64 holds G = K_td + R
+    Ntk,             // NTK, variances or full
+    NngpDiagLevel1,  // NNGP variances at level 1: like NngpDiag, and r64 already holds the residual of z64
+};
+
+struct PredictCall {
+    hipStream_t s = nullptr;
+    const double* xt = nullptr;        // the query rows (x_test = None: the training rows)
+    const double* qt = nullptr;        // their |x|^2 / d
+    const double* ktd = nullptr;       // cross kernel of `get`, [mp, np] (x_test = None: K_td = K_dd (estimator.py:37-40); its padding is zero)
+    const double* ktd_nngp = nullptr;  // NTK covariance: the NNGP cross kernel
+    int64_t mt = 0, mp = 0;
+    bool on_train = false, is_ntk = false, want_cov = false, full = false;
+    bool compact_train = false;  // x_test = None and K_dd's rows have stride ld != np: they are copied to the compact cross buffer
+    bool serving = false;        // Z = K_td X with the explicit float64 inverse: one product, no solves
+    double *mean = nullptr, *var_or_cov = nullptr;
+    // what the covariance stage found out
+    bool z_valid = false;           // z64 ends up holding the rows K_td (K + reg I)^-1 (to first order): the mean can be corrected through them
+    bool used_i8 = false;           // a first residual of this call's covariance took the int8 pipe
+    bool i8_check_pending = false;  // first level-1 predict of a fit on the int8 residual: it waits for its own guard estimate
+    CovCheck check = CovCheck::None;
+};
+
 // ---- api_predict.hip: workspaces, the factor's consumers, the posterior ----
 int ensure_predict_capacity(nngp_model* m, int64_t mt, bool need_ktd);
 int ensure_full_cov_capacity(nngp_model* m, int64_t mt);
@@ -228,14 +310,6 @@ int ensure_refine_capacity(nngp_model* m, int64_t mp);
 int ensure_lt_alloc(nngp_model* m);
 int ensure_lt(nngp_model* m, hipStream_t s);
 int ensure_lt_split(nngp_model* m, hipStream_t s);
-bool use_i8s(const nngp_model* m, int64_t mp);
-bool use_i8s_fine(const nngp_model* m, int64_t mp);
-int i8s_planes_policy(const nngp_model* m);
-int ensure_i8s(nngp_model* m, int64_t mp, I8Planes& pk, int planes);
-int i8s_cut_planes(nngp_model* m, I8Planes& pk, const double* kmat, int64_t kld, hipStream_t s);
-int i8s_product_rows(nngp_model* m, I8Planes& pk, const double* kmat, int64_t kld, double* out, const double* cin, double beta,
-                     double alpha, double* z, double gamma, int64_t mp, hipStream_t s, int grade);
-int residual_rows(nngp_model* m, double* out, const double* rhs, double* z, int64_t mp, hipStream_t s, bool first_residual);
 int tri_join(nngp_model* m, hipStream_t s);
 int tri_fork(nngp_model* m, hipStream_t s);
 bool use_split_solves(const nngp_model* m, int64_t mp);
@@ -245,15 +319,31 @@ SolvePath solve_path(const nngp_model* m, int64_t mp);  // which triangular solv
 // the float32 L^T (ensure_lt) is the backward operand of these; the split paths read the split copy of L^T (ensure_lt_split)
 inline bool needs_lt32(SolvePath p) { return p == SolvePath::Recursion128 || p == SolvePath::BlocksF32; }
 bool cg_from_the_start(const nngp_model* m, int64_t mp);
+hipStream_t early_cut_stream(const nngp_model* m, int64_t mp);  // where a predict cuts K's digit planes beside its first kernels
+int record_cg_gate(nngp_model* m, hipStream_t s);               // from here on `s` the deferred alpha CG may run
 int tickets_reserve(const nngp_model* m);
 int tickets_check(nngp_model* m, bool wait);
 int apply_forward_f32(nngp_model* m, int64_t mp, hipStream_t s);
 int apply_inverse_f32(nngp_model* m, int64_t mp, hipStream_t s);
 int refined_solve_rows(nngp_model* m, const double* rhs, int64_t mp, int sweeps, bool final_residual, hipStream_t s,
-                       bool measure = false);
+                       bool measure = false, ResidualNote* note = nullptr);
 int rows_pcg_continue(nngp_model* m, int64_t mp, int max_iters, hipStream_t s);
 int build_cross(nngp_model* m, const double* xt, const double* qt, int64_t mt, int64_t mp, bool nngp, double* out,
                 hipStream_t s);
+// ---- residual_i8.hip: the covariance's residual products, float64 grade on the int8 matrix pipe where it pays and may be trusted ----
+bool use_i8s(const nngp_model* m, int64_t mp);
+int i8s_reserve(nngp_model* m, int64_t mp, int32_t cov_mode);  // nngp_model_reserve: what a predict would allocate for the path
+void i8s_kernel_changed(nngp_model* m);                        // K has new entries: planes stale, the fit trusted again
+int cut_planes_early(nngp_model* m, PredictCall& c);
+int residual_rows(nngp_model* m, double* out, const double* rhs, double* z, int64_t mp, hipStream_t s, bool first_residual,
+                  ResidualNote* note = nullptr);
+int kaux_product_rows(nngp_model* m, double* out, double* z, int64_t mp, hipStream_t s);  // NTK: out = z K_aux
+void take_in_guard_word(nngp_model* m);
+int record_i8_guard_estimate(nngp_model* m, PredictCall& c);
+int first_guard_verdict(nngp_model* m, PredictCall& c, bool* redo);
+int i8s_timer_enable(nngp_model* m, int32_t enable);
+int i8s_timer_read(nngp_model* m, int64_t* launches, double* ms_total, double* flops_total, double* int8_ops_total);
+int i8s_residual_floor(nngp_model* m, double* ratio, int32_t* distrusted);
 // ---- api.hip ----
 int run_pending_solve(nngp_model* m, hipStream_t user, bool order_user, bool allow_partial = false);  // the deferred alpha CG
 }  // namespace nngp
