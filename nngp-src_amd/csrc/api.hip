@@ -2,7 +2,8 @@
 // device buffers of one GP fit.  Mirrors the three nested reference interfaces of SURVEY.md 8b:
 //   kernel_fn(x1, x2, get)                                  -> nngp_kernel_build
 //   gradient_descent_mse_ensemble(kernel_fn, X, Y, diag_reg) -> nngp_model_create / _fit
-//   predict_fn(x_test, get, compute_cov)                    -> nngp_model_predict
+//   predict_fn(x_test, get, compute_cov)                    -> nngp_model_predict  (api_predict.hip)
+// The deferred CG solve for alpha -- nngp_model_solve, _set_alpha, _alpha -- is in alpha_solve.hip.
 #include "model.h"
 
 namespace nngp {
@@ -330,10 +331,10 @@ static int model_create(nngp_model** out, int64_t n_cap, int64_t m_cap, int32_t 
     int prio_least = 0, prio_greatest = 0;  // the solve's many small kernels must not queue behind the covariance GEMMs
     if (hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) != hipSuccess) prio_least = prio_greatest = 0;
     if (rc == 0 && (hipStreamCreateWithPriority(&m->solve_stream, hipStreamNonBlocking, prio_greatest) != hipSuccess ||
-                    hipEventCreateWithFlags(&m->ev_ready, hipEventDisableTiming) != hipSuccess ||
+                    hipEventCreateWithFlags(&m->alpha_solve.ev_ready, hipEventDisableTiming) != hipSuccess ||
                     hipEventCreateWithFlags(&m->ev_lt, hipEventDisableTiming) != hipSuccess ||
-                    hipEventCreateWithFlags(&m->ev_solved, hipEventDisableTiming) != hipSuccess ||
-                    hipEventCreateWithFlags(&m->ev_predict, hipEventDisableTiming) != hipSuccess)) {
+                    hipEventCreateWithFlags(&m->alpha_solve.ev_solved, hipEventDisableTiming) != hipSuccess ||
+                    hipEventCreateWithFlags(&m->alpha_solve.ev_predict, hipEventDisableTiming) != hipSuccess)) {
         set_error("model_create: could not create the solve stream");
         rc = -1;
     }
@@ -391,11 +392,10 @@ int nngp_model_set_train(nngp_model* m, const double* x, const double* y, int64_
     hipStream_t s = (hipStream_t)stream;
     NNGP_REQUIRE(m != nullptr && x != nullptr && y != nullptr, "set_train: NULL argument");
     NNGP_REQUIRE(n > 0 && n <= m->n_cap, "set_train: n=%lld outside (0, n_cap=%lld]", (long long)n, (long long)m->n_cap);
-    NNGP_TRY(drop_pending_solve(m));
+    m->alpha_solve.plan.invalidate();
     m->n = n;
     m->np = round_up(n, TB);
-    m->built = m->factored = m->solved = false;
-    m->solve_pending = false;
+    m->built = m->factored = false;
     m->serving_ready = false;
     NNGP_HIP_CHECK(hipMemcpyAsync(m->x, x, sizeof(double) * n * m->d, hipMemcpyDeviceToDevice, s));
     NNGP_HIP_CHECK(hipMemcpyAsync(m->y, y, sizeof(double) * n * m->ny, hipMemcpyDeviceToDevice, s));
@@ -418,7 +418,7 @@ int nngp_model_build_rows(nngp_model* m, int64_t row_begin, int64_t row_end, voi
     hipStream_t s = (hipStream_t)stream;
     NNGP_REQUIRE(m != nullptr && m->have_train, "build_rows: call set_train first");
     NNGP_REQUIRE(0 <= row_begin && row_begin <= row_end && row_end <= m->n, "build_rows: bad row range");
-    NNGP_TRY(drop_pending_solve(m));
+    m->alpha_solve.plan.invalidate();
     BuildArgs a{};
     a.x1 = m->x; a.x2 = m->x; a.q1 = m->q; a.q2 = m->q;
     a.n1 = m->n; a.n2 = m->n; a.d = m->d;
@@ -451,15 +451,14 @@ int nngp_model_build_rows(nngp_model* m, int64_t row_begin, int64_t row_end, voi
     }
     NNGP_TRY(launch_zero_pad_f64(m->k64, m->ld, m->n, m->np, s));  // float64 GEMMs read the padded matrix
     m->built = true;  // the caller vouches for the remaining rows (all-gather) before factor
-    m->factored = m->solved = false;
-    m->solve_pending = false;
+    m->factored = false;
     return 0;
 }
 
 int nngp_model_factor_begin(nngp_model* m, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     NNGP_REQUIRE(m != nullptr && m->built, "factor: build the kernel rows first");
-    NNGP_TRY(drop_pending_solve(m));
+    m->alpha_solve.plan.invalidate();
     // a32 = float32(K) + reg I on the lower tiles; if the build already wrote it, only the last (partial + padding)
     // block row is left
     NNGP_TRY(launch_factor_input(m->k64, m->ld, m->a32, m->ld, m->n, m->np, m->reg_fac, m->reg_fac + m->trace_mean, s,
@@ -468,8 +467,7 @@ int nngp_model_factor_begin(nngp_model* m, void* stream) {
     m->a32_complete = false;
     NNGP_HIP_CHECK(hipMemsetAsync(m->clamped, 0, sizeof(int32_t), s));
     m->tri.bs = triinv_block(m->np);
-    m->factored = m->solved = false;
-    m->solve_pending = false;
+    m->factored = false;
     m->serving_ready = false;
     m->split.l_ready = m->split.lt_ready = false;  // set again by the look-ahead factorisation / factor_end
     m->split.split_panel = -1;
@@ -500,7 +498,7 @@ int nngp_model_factor_input_rows(nngp_model* m, int64_t row_begin, int64_t row_e
     hipStream_t s = (hipStream_t)stream;
     NNGP_REQUIRE(m != nullptr && m->built, "factor_input_rows: build the kernel rows first");
     NNGP_REQUIRE(0 <= row_begin && row_begin <= row_end && row_end <= m->n && shift_scale >= 1.0, "factor_input_rows: bad row range or shift");
-    NNGP_TRY(drop_pending_solve(m));
+    m->alpha_solve.plan.drop();
     m->reg_fac = m->reg * shift_scale;
     m->k64_partial = true;
     return launch_factor_input(m->k64, m->ld, m->a32, m->ld, m->n, m->np, m->reg_fac, m->reg_fac + m->trace_mean, s, row_begin, row_end);
@@ -526,20 +524,6 @@ int nngp_model_matvec_rows(nngp_model* m, const double* p, double* q, int64_t ro
     return launch_gemv_f64(m->k64 + row_begin * m->ld, m->ld, row_end - row_begin, m->n, p, 1, q, 1, 0.0, (hipStream_t)stream);
 }
 
-int nngp_model_set_alpha(nngp_model* m, const double* alpha, int32_t iters, double rel_residual, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    NNGP_REQUIRE(m != nullptr && m->factored && alpha != nullptr, "set_alpha: factor first");
-    NNGP_TRY(drop_pending_solve(m));
-    NNGP_HIP_CHECK(hipMemcpyAsync(m->alpha, alpha, sizeof(double) * m->n * m->ny, hipMemcpyDeviceToDevice, s));
-    m->solved = true;
-    m->solve_pending = false;
-    m->cg_partial = false;
-    m->have_alpha_event = false;  // alpha was written on the caller's stream, in order
-    m->iters = iters;
-    m->relres = rel_residual;
-    return 0;
-}
-
 int nngp_model_factor_end(nngp_model* m, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     NNGP_REQUIRE(m != nullptr && m->built, "factor_end: build the kernel rows first");
@@ -557,7 +541,9 @@ int nngp_model_factor_end(nngp_model* m, void* stream) {
         m->split.l_ready = true;
     }
     m->factored = true;
-    m->solved = false;
+    // (neutral beside the plain "not solved" this was: factor_begin has dropped the solve, and nngp_model_solve is refused between
+    // the two because `factored` is false)
+    m->alpha_solve.plan.invalidate();
     m->lt_ready = false;
     return 0;  // (aux_ready follows the kernel, not the factor: nngp_model_build_rows / nngp_model_append reset it)
 }
@@ -613,7 +599,7 @@ int nngp_model_append(nngp_model* m, const double* x_new, const double* y_new, i
                  (long long)m->n_cap);
     const int64_t n0 = m->n, n1 = n0 + b, np0 = m->np, np1 = round_up(n1, TB), r0 = (n0 / TB) * TB, rows = np1 - r0;
     NNGP_REQUIRE(r0 > 0, "append: the fitted model must have at least 128 rows");
-    NNGP_TRY(drop_pending_solve(m));
+    m->alpha_solve.plan.invalidate();
     NNGP_TRY(ensure_predict_capacity(m, rows, false));  // b32 / trsm_tmp workspace of the blocked solve
     // 1. data, diagonal, regulariser
     NNGP_HIP_CHECK(hipMemcpyAsync(m->x + n0 * m->d, x_new, sizeof(double) * b * m->d, hipMemcpyDeviceToDevice, s));
@@ -633,8 +619,6 @@ int nngp_model_append(nngp_model* m, const double* x_new, const double* y_new, i
     set_split_scale(m);
     m->n = n1;
     m->np = np1;
-    m->solved = false;
-    m->solve_pending = false;
     m->serving_ready = false;
     i8s_kernel_changed(m);
     // 2. kernel rows [n0, n1) against all n1 rows, their mirror image, and the new padding
@@ -674,136 +658,6 @@ int nngp_model_append(nngp_model* m, const double* x_new, const double* y_new, i
     m->lt_ready = false;
     m->aux_ready = false;
     (void)np0;
-    return 0;
-}
-
-// Runs the deferred CG solve for alpha (see nngp_model: solve_stream).  `user`: the stream whose later work needs alpha.
-constexpr int kSolveAhead = 6;  // run-ahead experiment (nngp_model_solve): the bench sizes converge in 5 / 6 iterations
-
-// Stopping tolerance of the early-stopped solve.  Measured at N = 32768 (ms per step / error of the corrected mean): 1e-6:
-// 150.0 / 8e-11, 1e-4: 147.5 / 4e-9, 1e-2: 145.9 / 2e-7.  1e-6 it is: the iteration count extrapolated from a solve stopped
-// at 1e-4 underestimates slowly converging fits (two of the sweep's 72 cases then missed the adaptive covariance).
-// (Round 2, level-1 variance: 1e-4 saves 2.2 of 113 ms; a two-staged stop -- 1e-4 only if reached within three iterations --
-// kept the adaptive covariance right, but the corrected means at N = 8192 / 32768 then sit 1.3e-6 / 4.8e-6 (elementwise)
-// from the oracle instead of 3e-9: not taken.)
-constexpr double kPartialTol = 1e-6;
-
-// iterations the solve needs (or would need) to reach pend_tol, from the rate it converged at
-static void note_solve(nngp_model* m, int it, double rr) {
-    int est = it;
-    if (rr > m->pend_tol && rr > 0.0 && rr < 1.0 && it > 0) est = (int)ceil(it * log(m->pend_tol) / log(rr));
-    if (est > m->iters) m->iters = est;
-    if (rr > m->relres) m->relres = rr;
-}
-
-// allow_partial: the caller can correct the mean through the covariance rows, so the CG may stop at kPartialTol.
-}  // extern "C"
-namespace nngp {
-int run_pending_solve(nngp_model* m, hipStream_t user, bool order_user, bool allow_partial) {
-    hipStream_t s = m->solve_stream;
-    auto join_tri = [&]() -> int {  // the preconditioner's inverted blocks: behind the factor (ev_ready), built here if nobody has yet
-        NNGP_HIP_CHECK(hipStreamWaitEvent(s, m->ev_ready, 0));
-        return tri_join(m, s);
-    };
-    if (!m->solve_pending) {
-        if (!m->cg_partial || allow_partial) {
-            // alpha was written on the solve stream: a caller on another stream than the one that triggered the solve
-            // still has to be ordered behind it (free once the event has completed)
-            if (order_user && m->solved && m->have_alpha_event) NNGP_HIP_CHECK(hipStreamWaitEvent(user, m->ev_solved, 0));
-            return 0;
-        }
-        // alpha itself is needed: take the stopped solve up again where it was (behind the last predict, whose mean
-        // correction may still be reading the residual this is about to update)
-        if (m->have_predict_event) NNGP_HIP_CHECK(hipStreamWaitEvent(s, m->ev_predict, 0));
-        int it = 0;
-        double rr = 0.0;
-        NNGP_TRY(join_tri());
-        NNGP_TRY(pcg_finish(m->k64, m->ld, m->n, m->reg, m->a32, m->ld, m->tri, m->np, m->pcg.xcol, m->pcg, m->cg_iters_done,
-                            m->pend_max_iters, m->pend_tol, &it, &rr, s, true));
-        NNGP_TRY(launch_strided_copy_f64(m->pcg.xcol, 1, m->alpha, m->ny, m->n, s));
-        m->cg_partial = false;
-        m->iters = 0;
-        m->relres = 0.0;
-        note_solve(m, it, rr);
-        NNGP_HIP_CHECK(hipEventRecord(m->ev_solved, s));
-        m->have_alpha_event = true;
-        if (order_user) NNGP_HIP_CHECK(hipStreamWaitEvent(user, m->ev_solved, 0));
-        else NNGP_HIP_CHECK(hipStreamSynchronize(s));
-        return 0;
-    }
-    m->solve_pending = false;
-    m->iters = 0;
-    m->relres = 0.0;
-    m->cg_partial = false;
-    const bool partial = allow_partial && m->ny == 1 && m->pend_tol < 1e-3 && NNGP_KNOB(0) != 128;
-    const double tol = partial ? ((NNGP_KNOB(3) >= 41 && NNGP_KNOB(3) <= 52) ? pow(10.0, -(double)(NNGP_KNOB(3) - 40)) : kPartialTol) : m->pend_tol;
-    NNGP_TRY(join_tri());
-    if (m->solve_ahead > 0) {
-        const int ahead = m->solve_ahead;
-        m->solve_ahead = 0;
-        int it = 0;
-        double rr = 0.0;
-        NNGP_TRY(pcg_finish(m->k64, m->ld, m->n, m->reg, m->a32, m->ld, m->tri, m->np, m->pcg.xcol, m->pcg, ahead,
-                            m->pend_max_iters, m->pend_tol, &it, &rr, s));
-        NNGP_TRY(launch_strided_copy_f64(m->pcg.xcol, 1, m->alpha, m->ny, m->n, s));
-        note_solve(m, it, rr);
-    } else {
-        NNGP_HIP_CHECK(hipStreamWaitEvent(s, m->ev_ready, 0));
-        if (m->gate_recorded) NNGP_HIP_CHECK(hipStreamWaitEvent(s, m->ev_gate, 0));  // see i8s_product_rows
-        for (int c = 0; c < m->ny; ++c) {
-            NNGP_TRY(launch_strided_copy_f64(m->y + c, m->ny, m->pcg.bcol, 1, m->n, s));
-            int it = 0;
-            double rr = 0.0;
-            NNGP_TRY(pcg_solve(m->k64, m->ld, m->n, m->reg, m->a32, m->ld, m->tri, m->np, m->pcg.bcol, m->pcg.xcol,
-                               m->pcg, m->pend_max_iters, tol, &it, &rr, s));
-            NNGP_TRY(launch_strided_copy_f64(m->pcg.xcol, 1, m->alpha + c, m->ny, m->n, s));
-            if (partial && rr > m->pend_tol) {
-                m->cg_partial = true;
-                m->cg_iters_done = it;
-            }
-            note_solve(m, it, rr);
-        }
-    }
-    NNGP_HIP_CHECK(hipEventRecord(m->ev_solved, s));
-    m->have_alpha_event = true;
-    if (order_user) NNGP_HIP_CHECK(hipStreamWaitEvent(user, m->ev_solved, 0));
-    else NNGP_HIP_CHECK(hipStreamSynchronize(s));
-    return 0;
-}
-
-}  // namespace nngp
-
-extern "C" {
-
-int nngp_model_solve(nngp_model* m, int32_t max_iters, double tol, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    NNGP_REQUIRE(m != nullptr && m->factored, "solve: factor first");
-    NNGP_REQUIRE(!m->k64_partial, "solve: this model holds only its own kernel rows (row-sharded layout): the caller drives the CG "
-                                  "(nngp_model_precond, nngp_model_matvec_rows) and hands alpha back with nngp_model_set_alpha");
-    NNGP_TRY(drop_pending_solve(m));
-    // default: 60 iterations; a factor with a raised shift preconditions worse by ~ sqrt(reg_fac / reg)
-    const double weak = (m->reg > 0.0 && m->reg_fac > m->reg) ? sqrt(m->reg_fac / m->reg) : 1.0;
-    m->pend_max_iters = max_iters > 0 ? max_iters : (int)fmin(2000.0, 60.0 * weak);
-    m->pend_tol = tol > 0.0 ? tol : 1e-10;
-    NNGP_HIP_CHECK(hipEventRecord(m->ev_ready, s));  // everything the solve reads has been enqueued on `s`
-    m->solve_pending = true;
-    m->solved = true;
-    if (NNGP_KNOB(7) == 3) return run_pending_solve(m, s, true);  // timing experiment: solve now, in stream order
-    if (NNGP_KNOB(0) & 32) return run_pending_solve(m, s, true, true);  // ... early-stopped (a later mean-only predict resumes it)
-    // (measured and dropped: starting the first six CG iterations here, on the solve stream, without waiting on the host
-    // (pcg_begin / pcg_finish) -- the CG then runs beside the posterior's float32 solves instead of under its float64
-    // GEMMs, and the two latency-bound kernel chains slow each other down by what the overlap gains: N = 32768: 155.8 vs
-    // 152.5 ms per step, N = 8192: 16.0 vs 15.3, N = 65536: 716 vs 706; the same with the solve stream at normal priority.
-    // Debug key 0 = 64 enables it for timing.)
-    if (m->ny == 1 && NNGP_KNOB(0) == 64) {
-        const int ahead = m->pend_max_iters < kSolveAhead ? m->pend_max_iters : kSolveAhead;
-        NNGP_HIP_CHECK(hipStreamWaitEvent(m->solve_stream, m->ev_ready, 0));
-        NNGP_TRY(tri_join(m, m->solve_stream));
-        NNGP_TRY(launch_strided_copy_f64(m->y, 1, m->pcg.bcol, 1, m->n, m->solve_stream));
-        NNGP_TRY(pcg_begin(m->k64, m->ld, m->n, m->reg, m->a32, m->ld, m->tri, m->np, m->pcg.bcol, m->pcg.xcol, m->pcg, ahead,
-                           m->solve_stream));
-        m->solve_ahead = ahead;
-    }
     return 0;
 }
 
@@ -895,19 +749,11 @@ int nngp_model_info(nngp_model* m, nngp_fit_info* info) {
     if (m->factored) NNGP_HIP_CHECK(hipMemcpy(&cl, m->clamped, sizeof(int32_t), hipMemcpyDeviceToHost));
     info->reg = m->reg;
     info->trace_mean = m->trace_mean;
-    info->rel_residual = m->relres;
-    info->refine_iters = m->iters;
+    info->rel_residual = m->alpha_solve.plan.relres;
+    info->refine_iters = m->alpha_solve.plan.iters;
     info->clamped_pivots = cl;
     info->n = m->n;
     info->n_padded = m->np;
-    return 0;
-}
-
-int nngp_model_alpha(nngp_model* m, double* alpha_out, void* stream) {
-    NNGP_REQUIRE(m != nullptr && m->solved && alpha_out != nullptr, "model_alpha: solve first");
-    NNGP_TRY(run_pending_solve(m, (hipStream_t)stream, true));
-    NNGP_HIP_CHECK(hipMemcpyAsync(alpha_out, m->alpha, sizeof(double) * m->n * m->ny, hipMemcpyDeviceToDevice,
-                                  (hipStream_t)stream));
     return 0;
 }
 

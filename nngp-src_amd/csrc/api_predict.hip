@@ -53,16 +53,6 @@ int ensure_full_cov_capacity(nngp_model* m, int64_t mt) {
     return 0;
 }
 
-// A CG that was started ahead (nngp_model_solve) reads y, K, the factor and the CG workspace: anything that is about to
-// overwrite those waits for it and drops it.
-int drop_pending_solve(nngp_model* m) {
-    if (m->solve_pending && m->solve_ahead > 0) NNGP_HIP_CHECK(hipStreamSynchronize(m->solve_stream));
-    m->solve_pending = false;
-    m->solve_ahead = 0;
-    m->cg_partial = false;
-    return 0;
-}
-
 // |L_ij| <= sqrt(max_i A_ii): scale of the float16 split copies of the factor, largest entry below 2^15
 void set_split_scale(nngp_model* m) {
     const double lmax = sqrt(fmax(m->diag_max, m->trace_mean) + m->reg_fac);
@@ -222,14 +212,6 @@ hipStream_t early_cut_stream(const nngp_model* m, int64_t mp) {
     return cs;
 }
 
-// From here on `s` the deferred alpha CG (solve stream) may run: run_pending_solve waits for the gate when one was recorded
-int record_cg_gate(nngp_model* m, hipStream_t s) {
-    if (m->ev_gate == nullptr) NNGP_HIP_CHECK(hipEventCreateWithFlags(&m->ev_gate, hipEventDisableTiming));
-    NNGP_HIP_CHECK(hipEventRecord(m->ev_gate, s));
-    m->gate_recorded = true;
-    return 0;
-}
-
 // a persistent solve that gave up waiting left its error word behind: report it once, and keep the model off that path
 int tickets_check(nngp_model* m, bool wait) {
     const int e = tk_poll_error(m->tk, wait);
@@ -261,7 +243,7 @@ int apply_forward_f32(nngp_model* m, int64_t mp, hipStream_t s) {
 static int apply_forward_untimed(nngp_model* m, int64_t mp, hipStream_t s) {
     // While the deferred alpha CG runs on its own stream (from the int8 residual's gate on), the solves' persistent update grids
     // leave it some compute units (debug key 13 = n: n units; default 0 = none -- see DESIGN_NOTES R4)
-    m->split.solve_reserve = (m->gate_recorded && NNGP_KNOB(13) > 0) ? NNGP_KNOB(13) : 0;
+    m->split.solve_reserve = (m->alpha_solve.gate_recorded && NNGP_KNOB(13) > 0) ? NNGP_KNOB(13) : 0;
     switch (solve_path(m, mp)) {
     case SolvePath::Recursion128: return trsm_rlt_f32(m->b32, m->np, mp, m->a32, m->ld, m->dinv, m->np, s);
     case SolvePath::Tickets: return tk_solve(m->tk, m->b32, m->np, mp, m->np, m->split, false, s, tickets_reserve(m));
@@ -284,7 +266,7 @@ int apply_inverse_f32(nngp_model* m, int64_t mp, hipStream_t s) {
         NNGP_HIP_CHECK(hipEventRecord(m->ev_lt, m->solve_stream));
     }
     NNGP_TRY(apply_forward_f32(m, mp, s));
-    if (NNGP_KNOB(2) == 10 && !m->gate_recorded && m->solve_pending) {  // timing experiment: the deferred alpha CG starts with the backward solve
+    if (NNGP_KNOB(2) == 10 && !m->alpha_solve.gate_recorded && m->alpha_solve.plan.pending) {  // timing experiment: the deferred alpha CG starts with the backward solve
         NNGP_TRY(record_cg_gate(m, s));
     }
     if (lt_aside) NNGP_HIP_CHECK(hipStreamWaitEvent(s, m->ev_lt, 0));
@@ -413,7 +395,7 @@ constexpr double kSweepEstThr = 3e-7;
 // Stage 1: argument checks, the call's facts, capacity.  (no rows: c.mt == 0 and nothing is allocated)
 static int predict_open(nngp_model* m, const double* x_test, int64_t mt, int32_t cov_mode, double* mean, double* var_or_cov,
                         hipStream_t s, PredictCall& c) {
-    NNGP_REQUIRE(m != nullptr && m->solved, "predict: fit the model first");
+    NNGP_REQUIRE(m != nullptr && m->alpha_solve.plan.solved, "predict: fit the model first");
     NNGP_REQUIRE(cov_mode >= NNGP_COV_NONE && cov_mode <= NNGP_COV_FULL, "predict: bad cov_mode");
     NNGP_REQUIRE(mean != nullptr && (cov_mode == NNGP_COV_NONE || var_or_cov != nullptr), "predict: NULL output");
     c.on_train = (x_test == nullptr);
@@ -683,7 +665,7 @@ static int weak_iters_threshold(CovCheck check) {
     return (check == CovCheck::NngpDiagLevel1 || check == CovCheck::NngpFull) ? 7 : 8;
 }
 static int preconditioner_is_weak(nngp_model* m, const PredictCall& c, bool* weak_out) {
-    bool weak = m->iters >= weak_iters_threshold(c.check) || m->reg_fac > m->reg;
+    bool weak = m->alpha_solve.plan.iters >= weak_iters_threshold(c.check) || m->reg_fac > m->reg;
     if (!weak && c.check == CovCheck::Ntk) {
         // NTK below 6 iterations: the count alone does not separate 4e-8 (N = 16384, d = 256: 4 iterations) from 5e-5
         // (N = 907, d = 2, four layers, diag_reg 1e-4: also 4).  What the two sweeps removed does: 16-byte read-back.
@@ -695,7 +677,7 @@ static int preconditioner_is_weak(nngp_model* m, const PredictCall& c, bool* wea
     }
     // the row flag is the backstop for fits whose alpha solve says nothing (it converged in < 3 iterations, e.g.
     // y = 0); otherwise the iteration count decides and the call stays asynchronous
-    if (!weak && c.check != CovCheck::Ntk && m->iters < 3) {
+    if (!weak && c.check != CovCheck::Ntk && m->alpha_solve.plan.iters < 3) {
         NNGP_HIP_CHECK(hipMemcpyAsync(m->rows.host + 1, m->rows.live + 1, sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
         NNGP_HIP_CHECK(hipStreamSynchronize(c.s));
         weak = m->rows.host[1] > 0;
@@ -731,7 +713,7 @@ static int write_mean(nngp_model* m, const PredictCall& c) {
     const int64_t n = m->n, np = m->np, mt = c.mt;
     for (int col = 0; col < m->ny; ++col)
         NNGP_TRY(launch_gemv_f64(c.ktd, np, mt, n, m->alpha + col, m->ny, c.mean + col, m->ny, 0.0, c.s));
-    if (m->cg_partial && c.z_valid) {
+    if (m->alpha_solve.plan.partial && c.z_valid) {
         // the CG stopped at a_k with residual r_k = y - A a_k (still in the CG workspace):
         //   K_td A^-1 y = K_td a_k + (K_td A^-1) r_k = K_td a_k + Z r_k + (K_td A^-1 - Z) r_k,
         // and the last term is the product of two small errors (rows: <= 1e-3 relative; r_k: <= 1e-6 |y|)
@@ -752,7 +734,7 @@ extern "C" {
 // afterwards predict forms Z = K_td X with ONE float64 product and no solves.
 int nngp_model_prepare_serving(nngp_model* m, void* stream) {
     hipStream_t s = (hipStream_t)stream;
-    NNGP_REQUIRE(m != nullptr && m->solved, "prepare_serving: fit the model first");
+    NNGP_REQUIRE(m != nullptr && m->alpha_solve.plan.solved, "prepare_serving: fit the model first");
     NNGP_REQUIRE(!m->k64_partial, "prepare_serving: not with the row-sharded layout (the model holds only its own kernel rows)");
     if (m->get != NNGP_GET_NNGP) return 0;  // the NTK covariance has no second-order formula to absorb the inverse's error
     NNGP_TRY(run_pending_solve(m, s, true));  // its iteration count says how good the preconditioner is
@@ -765,7 +747,7 @@ int nngp_model_prepare_serving(nngp_model* m, void* stream) {
         NNGP_HIP_CHECK(hipDeviceSynchronize());
         NNGP_TRY(dev_alloc(&m->ainv64, m->np_cap * m->np_cap));
     }
-    const bool weak = m->iters >= 8 || m->reg_fac > m->reg;
+    const bool weak = m->alpha_solve.plan.iters >= 8 || m->reg_fac > m->reg;
     // The serving predictions SQUARE the inverse's error (second-order formula) on top of a cancellation of 1e3 .. 1e6: the
     // inverse has to converge to float64 accuracy proper, and the COARSE int8 residual's floor (2^-32 of the row maxima) stops the
     // sweeps four digits short of it -- measured: 4e-3 in the serving variances at N = 2500 against 1e-7 (scripts/i8s_hard_case.py).
@@ -803,7 +785,7 @@ static int predict_impl(nngp_model* m, const double* x_test, int64_t mt, int32_t
     NNGP_TRY(build_cross_kernel(m, c));
     take_in_guard_word(m);
     c.used_i8 = false;
-    m->gate_recorded = false;
+    open_gate_epoch(m);
     if (c.want_cov) NNGP_TRY(form_covariance(m, c));
     NNGP_TRY(run_pending_solve(m, c.s, true, c.z_valid));
     bool redo_cov = false;
@@ -817,9 +799,7 @@ static int predict_impl(nngp_model* m, const double* x_test, int64_t mt, int32_t
         if (weak) NNGP_TRY(continue_rows_by_cg(m, c));
     }
     NNGP_TRY(write_mean(m, c));
-    NNGP_HIP_CHECK(hipEventRecord(m->ev_predict, c.s));
-    m->have_predict_event = true;
-    return 0;
+    return record_predict_end(m, c.s);
 }
 
 int nngp_model_predict(nngp_model* m, const double* x_test, int64_t mt, int32_t cov_mode, double* mean,

@@ -24,8 +24,7 @@ void note_alloc();  // counts a device allocation (nngp_alloc_count)
 // A/B tests, entry point nngp_debug_set); in the product library NNGP_KNOB(i) is the constant 0 and every branch on it is
 // compiled out.  Keys:
 //   0  bit mask: 1, 2, 4 leaf-kernel ablations (wrong results); 1, 2, 8 split-float16 GEMM ablations (no loads / no MFMA /
-//      no C traffic; wrong results); 64 = start the alpha CG ahead, without waiting on the host (nngp_model_solve);
-//      128 = never stop the alpha CG early (no mean correction through the covariance rows)
+//      no C traffic; wrong results); 128 = never stop the alpha CG early (no mean correction through the covariance rows)
 //   3  (also) 40 + e = stopping tolerance 10^-e of the early-stopped alpha CG (scripts/partial_tol_study.py)
 //   1  block-column width of the look-ahead Cholesky (default 1024)
 //   2  1 = no look-ahead (recursion on one stream); 2 = trailing updates on the float32 MFMA; 3 = panel-solve product on the
@@ -38,13 +37,11 @@ void note_alloc();  // counts a device allocation (nngp_alloc_count)
 //   5  2 = CU-masked streams; 9 = no split-K in the float64 GEMM; 8 = plain blockIdx tile order in the float64 GEMM; 10 + v = tile-block shape of the split-float16 GEMM
 //   6  >= 128: block size of the inverted diagonal blocks (default 1024); 1 = fixed covariance sweeps only and no retry
 //      of a broken-down factorisation; 2..30 = e: row-flag threshold 10^-e of the adaptive covariance
-//   7  1 = 128-wide recursion in the posterior solves; any non-zero value = float32 solve path; 3 = CG solve in stream
-//      order instead of deferred
+//   7  1 = 128-wide recursion in the posterior solves; any non-zero value = float32 solve path
 //   5  (also) 1 = old level-1 variance formula (full float64 residual + preconditioned remainder)
 //   5  (also) 50..57 int8 residual path (residual_i8.hip: use_i8s, ensure_i8s); round 4: 58 = five digit planes of z instead of three rounded ones;
 //      59 = row statistics and float32 copy in passes of their own instead of the fused combination; 60 = K chunks of 16384 always;
 //      61 = the factor's inverted blocks built in line (not beside the first predict's cross-kernel build); 62 = digit planes of K row by row; 63 = per-layer ReLU recursion in the kernel build (no composite map); 64 = seven z planes in FINE products; 65 = an NTK model's NNGP kernel always in a build of its own
-//   0  (also) 32 = alpha CG runs in stream order inside nngp_model_solve, early-stopped (resumed by whoever needs alpha itself)
 //   8  round 4, grouped Cholesky (set BEFORE the model is created): bit 1 = the schedule with the panel solves off the update stream
 //      (potrf_lookahead.hip, potrf_lookahead_grouped_v4; needs its extra streams); with it: 2 = bulk panel solves on the panel stream itself; 4 = early part
 //      of the next group's first diagonal-block update on its own stream; 8 = helper grids behind the bulk solves; 16 = a far chunk's
@@ -400,7 +397,7 @@ struct PcgWork {
     unsigned* dot_ctr = nullptr;  // its arrival counter (wraps to 0 by itself)
     double* symv_part = nullptr;  // [np / 128][np]: per-tile partial results of the symmetric matrix-vector product
     int64_t symv_np = 0;          // its np (0: not allocated -> plain GEMV)
-    double* scal;       // device scalars [32]: 0..4 CG scalars, 6..7 trace / max of the diagonal, 8.. CG residual history
+    double* scal;       // device scalars [32]: 0..4 CG scalars, 6..7 trace / max of the diagonal, 8 |b|^2 of the CG
     double* host_scal;  // pinned host [32]
     // One CG iteration (from the second on: ~170 launches at N = 32768) captured once as a hipGraph and replayed (round 4); the key says
     // what the captured launches were built for -- any change of it (another size, other buffers) captures again.
@@ -409,11 +406,10 @@ struct PcgWork {
     int64_t graph_dims[4] = {0, 0, 0, 0};
     double graph_reg = 0.0;  // (the regulariser is a by-value kernel argument)
 };
-int pcg_begin(const double* k64, int64_t ld, int64_t n, double reg, const float* l32, int64_t ld32, const TriInv& ti,
-              int64_t np, const double* bcol, double* xcol, PcgWork& w, int ahead, hipStream_t s);
+// pcg_finish: the solve goes on after `iters_done` iterations (a solve stopped at a looser tolerance; the CG state in w is intact)
 int pcg_finish(const double* k64, int64_t ld, int64_t n, double reg, const float* l32, int64_t ld32, const TriInv& ti,
-               int64_t np, double* xcol, PcgWork& w, int ahead, int max_iters, double tol, int* iters_out,
-               double* relres_out, hipStream_t s, bool resume = false);
+               int64_t np, double* xcol, PcgWork& w, int iters_done, int max_iters, double tol, int* iters_out,
+               double* relres_out, hipStream_t s);
 int pcg_solve(const double* k64, int64_t ld, int64_t n, double reg, const float* l32, int64_t ld32,
               const TriInv& ti, int64_t np, const double* bcol, double* xcol, PcgWork& w, int max_iters,
               double tol, int* iters_out, double* relres_out, hipStream_t s);

@@ -1,4 +1,4 @@
-// Internal to the C-ABI layer (api.hip, api_predict.hip, residual_i8.hip, api_ops.hip): the model object that owns the device buffers of one GP fit, and the
+// Internal to the C-ABI layer (api.hip, alpha_solve.hip, api_predict.hip, residual_i8.hip, api_ops.hip): the model object that owns the device buffers of one GP fit, and the
 // helpers the entry points share.  Not installed; include/nngp_hip.h is the interface.
 #pragma once
 #include <stdarg.h>
@@ -8,6 +8,7 @@
 #include <mutex>
 #include "common.h"
 #include "i8_trust.h"
+#include "alpha_plan.h"
 #include <atomic>
 
 namespace nngp {
@@ -119,6 +120,28 @@ struct I8Residual {
         if (ev_i8) (void)hipEventDestroy(ev_i8);
     }
 };
+
+// The CG solve for alpha (alpha_solve.hip) is deferred: nngp_model_solve records where the factor is ready, and the solve runs on
+// the model's solve stream when alpha is first needed -- inside predict AFTER the covariance work has been enqueued, so that the
+// HBM-bound CG (float64 GEMV + float32 TRSVs) overlaps the MFMA-bound covariance products.  Its bookkeeping and its hand-offs:
+struct AlphaSolve {
+    AlphaPlan plan{};
+    hipEvent_t ev_ready = nullptr;    // caller's stream, nngp_model_solve: everything the solve reads has been enqueued
+    hipEvent_t ev_solved = nullptr;   // solve stream: alpha is written (plan.have_event: recorded at least once)
+    hipEvent_t ev_predict = nullptr;  // end of the last predict on its stream: it reads alpha and the CG residual
+    bool have_predict_event = false;
+    hipEvent_t ev_gate = nullptr;  // start of the covariance's int8 plane products on the caller's stream: a fresh solve waits for it
+    bool gate_recorded = false;    // ... in this predict (record_cg_gate, which creates the event when first used)
+
+    AlphaSolve() = default;
+    AlphaSolve(const AlphaSolve&) = delete;
+    ~AlphaSolve() {
+        if (ev_ready) (void)hipEventDestroy(ev_ready);
+        if (ev_solved) (void)hipEventDestroy(ev_solved);
+        if (ev_predict) (void)hipEventDestroy(ev_predict);
+        if (ev_gate) (void)hipEventDestroy(ev_gate);
+    }
+};
 }  // namespace nngp
 
 using namespace nngp;
@@ -133,7 +156,7 @@ struct nngp_model {
 
     int64_t n = 0, np = 0;
     int64_t ld = 0;  // leading dimension of k64 / a32 = np_cap, fixed so that rows can be appended in place
-    bool have_train = false, built = false, factored = false, solved = false;
+    bool have_train = false, built = false, factored = false;
     bool a32_built = false;  // the kernel build also wrote float32(K) + reg I on the lower tiles of a32 (fused factor input)
     // Row-sharded layout (round 4, nngp-src_amd/shard32.py): this rank's float64 kernel rows stay local, the float32 factor input is what
     // travels.  a32_complete: every row of a32 is in place (converted here or gathered) -- factor_begin only adds the padding;
@@ -196,18 +219,14 @@ struct nngp_model {
     int64_t ktd_aux_cap = 0;
 
     I8Residual i8;  // the covariance's residual products on the int8 matrix pipe (residual_i8.hip)
-    hipEvent_t ev_gate = nullptr;  // start of the covariance's int8 plane products on the caller's stream: the deferred alpha CG waits for it
-    bool gate_recorded = false;    // (record_cg_gate)
+    AlphaSolve alpha_solve;  // the deferred CG solve for alpha (alpha_solve.hip)
 
-    double reg = 0.0, trace_mean = 0.0, relres = 0.0;
+    double reg = 0.0, trace_mean = 0.0;
     // Diagonal shift of the float32 factor's input.  = reg, unless the float32 factorisation of K + reg I broke down
     // (pivots at the rounding-noise floor: cond * eps32 >> 1); nngp_model_factor then factors K + reg_fac I with a
     // larger shift.  The factor is only the preconditioner: alpha and the refined covariances still solve K + reg I.
     double reg_fac = 0.0;
-    int iters = 0;
-    // The CG solve for alpha is deferred: nngp_model_solve records where the factor is ready, and the solve runs on its
-    // own stream when alpha is first needed -- inside predict AFTER the covariance work has been enqueued, so that the
-    // HBM-bound CG (float64 GEMV + float32 TRSVs) overlaps the MFMA-bound covariance products.
+    // The alpha CG's stream.  Idle until alpha is asked for: the triangular inverses, the split copy of L^T and the early plane cut use it too.
     hipStream_t solve_stream = nullptr;
     // The inverted 1024-blocks of the factor (tri: CG preconditioner, blocked solves) are built lazily: nngp_model_factor_end only marks
     // them stale; a predict right after the fit builds them on the look-ahead's panel stream beside its cross-kernel build (a chain of
@@ -218,20 +237,7 @@ struct nngp_model {
     EventPairTimer<32> trsm_t;
     double trsm_flops[decltype(trsm_t)::kMax] = {};  // np^2 mp per timed solve
     hipEvent_t ev_tri = nullptr, ev_tri_fork = nullptr;
-    hipEvent_t ev_ready = nullptr, ev_solved = nullptr;
     hipEvent_t ev_lt = nullptr;  // orders the split copy of L^T written on solve_stream (apply_inverse_f32)
-    hipEvent_t ev_predict = nullptr;  // end of the last predict on its stream: it reads alpha and the CG residual
-    bool have_predict_event = false;
-    bool solve_pending = false;
-    // Early stop (ny == 1): a predict that also forms the covariance rows Z ~ K_td (K + reg I)^-1 stops the CG at 1e-6 and
-    // corrects the mean through them: mu = K_td a_k + Z r_k (exact up to (K_td A^-1 - Z) r_k, the product of two small
-    // errors).  cg_partial: alpha holds a_k and the CG state in pcg is intact; anything that needs alpha itself resumes.
-    bool cg_partial = false;
-    bool have_alpha_event = false;  // ev_solved has been recorded at least once
-    int cg_iters_done = 0;
-    int solve_ahead = 0;  // > 0: the first `solve_ahead` CG iterations are already in flight on solve_stream (ny == 1)
-    int pend_max_iters = 60;
-    double pend_tol = 1e-10;
 
     ~nngp_model() {
         dev_free(x); dev_free(y); dev_free(q); dev_free(kdiag); dev_free(k64); dev_free(a32); dev_free(dinv);
@@ -244,13 +250,9 @@ struct nngp_model {
         dev_free(tri.tinv); dev_free(tri.xinv); dev_free(tri.partial); dev_free(tri.tmp);
         lookahead_destroy(la);
         if (solve_stream) (void)hipStreamDestroy(solve_stream);
-        if (ev_ready) (void)hipEventDestroy(ev_ready);
         if (ev_lt) (void)hipEventDestroy(ev_lt);
         if (ev_tri) (void)hipEventDestroy(ev_tri);
         if (ev_tri_fork) (void)hipEventDestroy(ev_tri_fork);
-        if (ev_solved) (void)hipEventDestroy(ev_solved);
-        if (ev_predict) (void)hipEventDestroy(ev_predict);
-        if (ev_gate) (void)hipEventDestroy(ev_gate);
         dev_free(split.planes); dev_free(split.counters); dev_free(split.planes_t); dev_free(split.planes_b); dev_free(split.row_inv);
         dev_free(split.ldiag); dev_free(split.dfrag); dev_free(split.dscale);
         tk_destroy(tk);
@@ -304,7 +306,6 @@ struct PredictCall {
 // ---- api_predict.hip: workspaces, the factor's consumers, the posterior ----
 int ensure_predict_capacity(nngp_model* m, int64_t mt, bool need_ktd);
 int ensure_full_cov_capacity(nngp_model* m, int64_t mt);
-int drop_pending_solve(nngp_model* m);
 void set_split_scale(nngp_model* m);
 int ensure_refine_capacity(nngp_model* m, int64_t mp);
 int ensure_lt_alloc(nngp_model* m);
@@ -320,7 +321,6 @@ SolvePath solve_path(const nngp_model* m, int64_t mp);  // which triangular solv
 inline bool needs_lt32(SolvePath p) { return p == SolvePath::Recursion128 || p == SolvePath::BlocksF32; }
 bool cg_from_the_start(const nngp_model* m, int64_t mp);
 hipStream_t early_cut_stream(const nngp_model* m, int64_t mp);  // where a predict cuts K's digit planes beside its first kernels
-int record_cg_gate(nngp_model* m, hipStream_t s);               // from here on `s` the deferred alpha CG may run
 int tickets_reserve(const nngp_model* m);
 int tickets_check(nngp_model* m, bool wait);
 int apply_forward_f32(nngp_model* m, int64_t mp, hipStream_t s);
@@ -344,6 +344,11 @@ int first_guard_verdict(nngp_model* m, PredictCall& c, bool* redo);
 int i8s_timer_enable(nngp_model* m, int32_t enable);
 int i8s_timer_read(nngp_model* m, int64_t* launches, double* ms_total, double* flops_total, double* int8_ops_total);
 int i8s_residual_floor(nngp_model* m, double* ratio, int32_t* distrusted);
-// ---- api.hip ----
-int run_pending_solve(nngp_model* m, hipStream_t user, bool order_user, bool allow_partial = false);  // the deferred alpha CG
+// ---- alpha_solve.hip: the deferred CG solve for alpha ----
+// Runs what is left of the solve (AlphaPlan::next).  `user`: the stream whose later work needs alpha; order_user = false: the host waits instead.
+// allow_partial: the caller can correct the mean through the covariance rows, so the CG may stop at kPartialTol.
+int run_pending_solve(nngp_model* m, hipStream_t user, bool order_user, bool allow_partial = false);
+void open_gate_epoch(nngp_model* m);                   // a predict starts: no gate recorded yet
+int record_cg_gate(nngp_model* m, hipStream_t s);      // from here on `s` a fresh solve may run
+int record_predict_end(nngp_model* m, hipStream_t s);  // a predict has enqueued its last read of alpha and the CG residual
 }  // namespace nngp

@@ -152,7 +152,7 @@ static int i8s_product_rows(nngp_model* m, I8Planes& pk, const double* kmat, int
         const int64_t slab = mb * np;
         NNGP_TRY(launch_i8s_slice_rows(z + r0 * np, np, mb, np, ns_z, nullptr, w.zscale, w.zplanes, m->np_cap, (w.z_rows + 256) * m->np_cap, s,
                                        round_z ? z + r0 * np : nullptr));
-        if (r0 == 0 && grade == I8_COARSE && !m->gate_recorded && NNGP_KNOB(2) != 8 && NNGP_KNOB(2) != 9 && !cg_from_the_start(m, mp)) {
+        if (r0 == 0 && grade == I8_COARSE && !m->alpha_solve.gate_recorded && NNGP_KNOB(2) != 8 && NNGP_KNOB(2) != 9 && !cg_from_the_start(m, mp)) {
             // The deferred alpha CG (solve stream) starts HERE, not with the blocked solves before this product: its hundreds of small
             // GEMV launches settle on compute units between the solves' persistent split-float16 launches (which need a whole unit's
             // LDS) and cost them 3.7 ms at N = 32768 (scripts/cov_alone.py); beside this one long launch they fit the wave slots and
@@ -177,7 +177,7 @@ static int i8s_product_rows(nngp_model* m, I8Planes& pk, const double* kmat, int
     }
     if (fuse_rows) note->fused = true;
     // timing experiment: the CG starts when the product has ended
-    if (grade == I8_COARSE && !m->gate_recorded && NNGP_KNOB(2) == 9) NNGP_TRY(record_cg_gate(m, s));
+    if (grade == I8_COARSE && !m->alpha_solve.gate_recorded && NNGP_KNOB(2) == 9) NNGP_TRY(record_cg_gate(m, s));
     return 0;
 }
 

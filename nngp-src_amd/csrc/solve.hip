@@ -497,13 +497,11 @@ int launch_gemv_f64(const double* a, int64_t lda, int64_t rows, int64_t cols, co
 
 // Preconditioned CG for (K + reg I) x = b in float64; M^-1 = (L L^T)^-1 with the float32 factor.
 // The scalars (rz, pAp, alpha, beta) live on the device; the host only reads |r|^2 to decide when to stop.  Two phases:
-//   pcg_begin  enqueues x = 0, r = b and `ahead` iterations WITHOUT waiting (|b|^2 and the |r|^2 of every iteration go to
-//              w.scal[8...]); iterating past convergence is harmless (the update kernels take alpha = beta = 0 when their
-//              denominators vanish), so the solve can run on its own stream from the moment the factor is ready;
-//   pcg_finish waits, reads the history, and continues one iteration at a time if `ahead` were not enough.
+//   pcg_begin  enqueues x = 0, r = b and |b|^2 (on its way to the host) WITHOUT waiting;
+//   pcg_finish waits, and iterates one step at a time from iteration `iters_done` on.  iters_done > 0: the solve was stopped after
+//              that many iterations at a looser tolerance and the CG state in w is intact -- it goes on from there.
 namespace {
-constexpr int kPcgHist = 8;       // w.scal[8] = |b|^2, w.scal[9 + it] = |r|^2 after iteration it
-constexpr int kPcgMaxAhead = 22;  // w.scal has 32 slots
+constexpr int kPcgHist = 8;  // w.scal[8] = |b|^2
 
 int pcg_iteration(const double* k64, int64_t ld, int64_t n, double reg, const float* l32, int64_t ld32, const TriInv& ti,
                   int64_t np, double* xcol, PcgWork& w, int it, double* rr_out, hipStream_t s) {
@@ -538,44 +536,25 @@ int precond_apply(const float* l32, int64_t ld32, const TriInv& ti, int64_t n, i
     return 0;
 }
 
-int pcg_begin(const double* k64, int64_t ld, int64_t n, double reg, const float* l32, int64_t ld32, const TriInv& ti,
-              int64_t np, const double* bcol, double* xcol, PcgWork& w, int ahead, hipStream_t s) {
-    NNGP_REQUIRE(ahead >= 0 && ahead <= kPcgMaxAhead, "pcg_begin: at most %d iterations ahead", kPcgMaxAhead);
+static int pcg_begin(int64_t n, const double* bcol, double* xcol, PcgWork& w, hipStream_t s) {
     NNGP_HIP_CHECK(hipMemsetAsync(xcol, 0, sizeof(double) * n, s));
     NNGP_HIP_CHECK(hipMemcpyAsync(w.r, bcol, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
     hipLaunchKernelGGL(k_dot, dim3(kDotBlocks), dim3(256), 0, s, bcol, bcol, n, w.scal + kPcgHist, w.dot_part, w.dot_ctr);
-    for (int it = 0; it < ahead; ++it)
-        NNGP_TRY(pcg_iteration(k64, ld, n, reg, l32, ld32, ti, np, xcol, w, it, w.scal + kPcgHist + 1 + it, s));
-    NNGP_HIP_CHECK(hipMemcpyAsync(w.host_scal + kPcgHist, w.scal + kPcgHist, sizeof(double) * (1 + ahead), hipMemcpyDeviceToHost, s));
+    NNGP_HIP_CHECK(hipMemcpyAsync(w.host_scal + kPcgHist, w.scal + kPcgHist, sizeof(double), hipMemcpyDeviceToHost, s));
     return 0;
 }
 
-// resume: the solve was stopped after `ahead` iterations at a looser tolerance (the CG state in w is intact): go on from there.
 int pcg_finish(const double* k64, int64_t ld, int64_t n, double reg, const float* l32, int64_t ld32, const TriInv& ti,
-               int64_t np, double* xcol, PcgWork& w, int ahead, int max_iters, double tol, int* iters_out,
-               double* relres_out, hipStream_t s, bool resume) {
+               int64_t np, double* xcol, PcgWork& w, int iters_done, int max_iters, double tol, int* iters_out,
+               double* relres_out, hipStream_t s) {
     NNGP_HIP_CHECK(hipStreamSynchronize(s));
     const double bnorm2 = w.host_scal[kPcgHist];
-    int iters = resume ? ahead : 0;
+    int iters = iters_done;
     double relres = 0.0;
     if (bnorm2 > 0.0) {
         relres = 1.0;
         bool done = false;
-        for (int it = 0; it < ahead && !resume; ++it) {  // the iterations that ran ahead: where did the residual first meet tol?
-            const double rel = sqrt(w.host_scal[kPcgHist + 1 + it] / bnorm2);
-            if (!(rel == rel)) {  // NaN: the preconditioner is unusable
-                set_error("pcg_solve: residual became NaN at iteration %d", it + 1);
-                return -3;
-            }
-            if (!done) {
-                iters = it + 1;
-                relres = rel;
-                if (rel <= tol) done = true;
-            } else if (rel < relres) {
-                relres = rel;  // the extra iterations only polish
-            }
-        }
-        for (int it = ahead; it < max_iters && !done; ++it) {
+        for (int it = iters_done; it < max_iters && !done; ++it) {
             // Iterations >= 1 launch the same kernels with the same arguments: they can be captured once as a hipGraph and replayed
             // (debug key 14 = 2).  Measured (round 4, scripts/cov_alone.py, N = 32768): CG alone 11.8 ms either way, covariance + mean with
             // the CG beside it 35.7 ms either way -- the ~170 launches of an iteration are bound by the GPU's own kernel-to-kernel
@@ -627,8 +606,8 @@ int pcg_finish(const double* k64, int64_t ld, int64_t n, double reg, const float
 int pcg_solve(const double* k64, int64_t ld, int64_t n, double reg, const float* l32, int64_t ld32,
               const TriInv& ti, int64_t np, const double* bcol, double* xcol, PcgWork& w, int max_iters,
               double tol, int* iters_out, double* relres_out, hipStream_t s) {
-    NNGP_TRY(pcg_begin(k64, ld, n, reg, l32, ld32, ti, np, bcol, xcol, w, 0, s));
-    return pcg_finish(k64, ld, n, reg, l32, ld32, ti, np, xcol, w, 0, max_iters, tol, iters_out, relres_out, s, false);
+    NNGP_TRY(pcg_begin(n, bcol, xcol, w, s));
+    return pcg_finish(k64, ld, n, reg, l32, ld32, ti, np, xcol, w, 0, max_iters, tol, iters_out, relres_out, s);
 }
 
 }  // namespace nngp

@@ -233,6 +233,50 @@ def test_append_rows_matches_full_refit(n0, b, ncap):
     inc.close()
 
 
+def test_a_stopped_alpha_solve_is_dropped_by_set_alpha_and_by_append():
+    """A predict with a covariance leaves the alpha CG stopped at 1e-6 (test_early_stopped_cg_mean_correction: this shape needs 3 to 8
+    iterations to 1e-10, so it stops; the stopped state has no public observable).  Whoever then installs alpha (nngp_model_set_alpha)
+    or changes what alpha solves (nngp_model_append) must drop the stopped solve: nothing may resume it over the installed alpha, and
+    nothing may pass its a_k off as the alpha of the extended fit."""
+    lib, p = _lib_mod.load(), _lib_mod.ptr
+    n, m, d, b = 3000, 100, 24, 128
+    x, y = synth.synthetic_queries(n + b, d, seed=21)
+    xt, _ = synth.synthetic_queries(m, d, seed=22)
+    a = o.make_arch(2)
+
+    def stopped(n_cap):
+        model = GPModel(n_cap, d, a.w_std, a.b_std, diag_reg=1e-3)
+        model.set_train(x[:n], y[:n]); model.build_rows(0, n); model.factor(); model.solve()   # no info(): the solve stays deferred
+        model.predict(xt, cov="diag")                                                          # ... and stops early
+        return model
+
+    twin = GPModel(n, d, a.w_std, a.b_std, diag_reg=1e-3).fit(x[:n], y[:n])
+    two_a = (2.0 * twin.alpha()).contiguous()
+    # set_alpha on a stopped solve
+    model = stopped(n)
+    assert lib.nngp_model_set_alpha(model.handle, p(two_a), 5, 1e-11, _lib_mod.stream_ptr()) == 0
+    assert torch.equal(model.alpha(), two_a)                                                   # alpha() had nothing to resume
+    info = model.info()
+    assert info["refine_iters"] == 5 and info["rel_residual"] == 1e-11, info
+    assert lib.nngp_model_set_alpha(twin.handle, p(two_a), 5, 1e-11, _lib_mod.stream_ptr()) == 0
+    assert np.array_equal(model.predict(xt, cov=False), twin.predict(xt, cov=False))
+    assert torch.equal(model.alpha(), two_a)
+    model.close(); twin.close()
+    # append on a stopped solve
+    model = stopped(n + 200)
+    model.append(x[n:], y[n:], solve=False)
+    out = torch.empty((n + b, 1), dtype=torch.float64, device=G.dev())
+    rc = lib.nngp_model_alpha(model.handle, p(out), _lib_mod.stream_ptr())
+    assert rc < 0 and "solve first" in (lib.nngp_last_error() or b"").decode(), rc
+    model.solve()
+    info = model.info()
+    assert info["n"] == n + b and info["rel_residual"] < 1e-9, info
+    ref = GPModel(n + b, d, a.w_std, a.b_std, diag_reg=1e-3).fit(x, y)
+    a_inc, a_ref = model.alpha().cpu().numpy(), ref.alpha().cpu().numpy()
+    assert np.linalg.norm(a_inc - a_ref) <= 1e-7 * np.linalg.norm(a_ref)
+    model.close(); ref.close()
+
+
 @pytest.mark.parametrize("get,n,d,reg", [("nngp", 2500, 20, 1e-3), ("ntk", 1300, 16, 1e-3), ("nngp", 2706, 3, 1e-4), ("nngp", 130, 5, 1e-3)])
 def test_serving_mode_matches_the_solve_path(get, n, d, reg):
     """nngp_model_prepare_serving: predictions through the explicit float64 inverse against the solve path at level 3
