@@ -63,6 +63,9 @@ ARD_ABI_SYMBOLS = ("nngp_mll_reserve_ard", "nngp_mll_evaluate_ard", "nngp_mll_lo
 ADDITIVE_ABI_SYMBOLS = ("nngp_kernel_build_additive", "nngp_kernel_diag_additive", "nngp_model_create_additive")
 MAX_GROUPS = 1024
 
+# include/nngp_additive_mll.h: the additive kernel's evidence and its gradient, term weights included, on the nngp_mll handle
+ADDITIVE_MLL_ABI_SYMBOLS = ("nngp_mll_reserve_additive", "nngp_mll_evaluate_additive", "nngp_mll_additive_terms")
+
 # include/nngp_pool.h: batch-aware pool selection (greedy by conditional variance); GPU library only (no host build)
 POOL_ABI_SYMBOLS = ("nngp_pool_select_greedy",)
 
@@ -142,6 +145,7 @@ def load(knobs: bool = False):
     bind_loo_prototypes(lib)
     bind_ard_prototypes(lib)
     bind_additive_prototypes(lib)
+    bind_additive_mll_prototypes(lib)
     bind_pool_prototypes(lib)
     bind_sparse_prototypes(lib)
     bind_sparse_evidence_prototypes(lib)
@@ -311,6 +315,18 @@ def bind_additive_prototypes(lib):
     lib.nngp_kernel_diag_additive.argtypes = [vp, i64, i32, archp, groupsp, vp, vp, vp]
     lib.nngp_model_create_additive.argtypes = [ctypes.POINTER(vp), i64, i64, i32, i32, archp, groupsp, i32, dbl, i32]
     for name in ADDITIVE_ABI_SYMBOLS:
+        getattr(lib, name).restype = ctypes.c_int
+    return lib
+
+
+def bind_additive_mll_prototypes(lib):
+    """Argument and result types of include/nngp_additive_mll.h (the HIP library only)."""
+    vp, i32, dbl = ctypes.c_void_p, ctypes.c_int32, ctypes.c_double
+    pd = ctypes.POINTER(dbl)
+    lib.nngp_mll_reserve_additive.argtypes = [vp, ctypes.POINTER(NngpGroups)]
+    lib.nngp_mll_evaluate_additive.argtypes = [vp, ctypes.POINTER(NngpArchAct), pd, dbl, i32, pd, pd, pd, vp]
+    lib.nngp_mll_additive_terms.argtypes = [vp, pd, i32]
+    for name in ADDITIVE_MLL_ABI_SYMBOLS:
         getattr(lib, name).restype = ctypes.c_int
     return lib
 

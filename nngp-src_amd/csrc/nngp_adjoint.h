@@ -45,14 +45,29 @@ struct MllArgs {
     int64_t np;
 };
 
+// The terms of the additive kernel over feature groups (nngp_mll_additive.hip): term 0 is the whole input, term t >= 1 group t - 1
+struct AddTerms {
+    int n_terms;
+    const int* gbegin;    // [n_terms - 1]: the groups' feature ranges, zero-weight groups included
+    const int* gend;
+    const double* tw;     // [n_terms]: w0, then w_g
+    double* tpart;        // [2 n_terms][nparts]: per term <seed 0, K^(t)> and <seed 1, K^(t)> of the tile
+};
+
 // NLC: room for n_dense <= NLC layers (the per-entry state lives in registers, so its size must be known at compile time).
 // LOO: the rank-two seed 1/2 (alpha_i u_j + u_i alpha_j) instead of alpha_i alpha_j.
 // ARD: also keep what the reverse sweep holds once it has passed Dense layer 0 -- kbar = S_ij dK_ij/dK0_ij into cmat, and
 // qbar1 = S_ij dK_ij/dq_i, qbar2 = S_ij dK_ij/dq_j summed over the tile's columns / rows into qbar.  Tile (ti, tj) writes its row
 // part to slot tj and its column part to slot ti (a diagonal tile the sum of both), so every slot has one writer.  A diagonal
 // entry depends on q_i alone (exact diagonal), so its kbar belongs to qbar.
-template <int NLC, bool LOO, bool ARD = false>
-__device__ __forceinline__ void adjoint_tile(const MllArgs& a, const ArchDev& arch) {
+// ADD: K = sum_t w_t K^(t) (include/nngp_additive_mll.h).  The tile is walked once per term, in the table's order: the term's Gram
+// tile over its feature range with its own 1 / d_t, for a group also both slices' |x_t|^2 / d_t from the SAME staged values in the
+// SAME order as the Gram entry (k_build_add's rule: identical slices give k == q == q' bit for bit and take the diagonal form,
+// whose derivative goes through the k chain alone), the q chain, then per entry the forward recursion, the term's value times both
+// seeds into the term's two halves, and -- unless w_t == 0 -- the reverse sweep from the seeds times w_t into the shared
+// accumulators.  With one term of weight 1 every operation of the plain pass is repeated in its order.
+template <int NLC, bool LOO, bool ARD = false, bool ADD = false>
+__device__ __forceinline__ void adjoint_tile(const MllArgs& a, const ArchDev& arch, const AddTerms& add = AddTerms{}) {
     __shared__ __attribute__((aligned(16))) double sm[2 * MT * MLD];  // the two row panels, then the Gram tile [MT][MT + 1]
     __shared__ double qs[NLC][2 * MT];  // rows | columns: q at the input of Dense layer l
     __shared__ double rq[NLC][2 * MT];  // 1 / (4 pi q') with q' after Dense layer l; 0 where q' = 0 (the q = 0 rule)
@@ -60,7 +75,9 @@ __device__ __forceinline__ void adjoint_tile(const MllArgs& a, const ArchDev& ar
     __shared__ double red[256];
     // ARD: [seed][row][tc] and [seed][column][tr] -- every thread sums into slots of its own, in the order of its entries
     __shared__ double rsum[ARD ? 2 : 1][ARD ? MT : 1][17], csum[ARD ? 2 : 1][ARD ? MT : 1][17];
+    __shared__ double qg[ADD ? 2 * MT : 1];  // ADD: rows | columns, a group's |x_t|^2 / d_t
     static_assert(MT * (MT + 1) <= 2 * MT * MLD, "the Gram tile aliases the panels");
+    static_assert(!(ARD && ADD), "relevances together with groups are not covered");
     const int tid = threadIdx.x, tc = tid & 15, tr = tid >> 4;
     if constexpr (ARD) {
         for (int e = tid; e < 2 * MT * 17; e += 256) (&rsum[0][0][0])[e] = (&csum[0][0][0])[e] = 0.0;
@@ -71,9 +88,7 @@ __device__ __forceinline__ void adjoint_tile(const MllArgs& a, const ArchDev& ar
     lower_tile(xcd_tile(blockIdx.x, tn * (tn + 1) / 2), &ti, &tj);
     const int64_t i0 = ti * MT, j0 = tj * MT;
     for (int e = tid; e < 65 * 4; e += 256) tab[e] = kTrigTab[e >> 2][e & 3];
-    if (tid < 2 * MT) {  // the q chain of the tile's rows and columns, in the kernel build's order of operations
-        const int64_t g = tid < MT ? i0 + tid : j0 + tid - MT;
-        double q = g < a.n ? a.q[g] : 0.0;
+    auto q_chain = [&](double q) {  // the q chain of the tile's rows and columns, in the kernel build's order of operations
 #pragma unroll
         for (int l = 0; l < NLC; ++l) {
             if (l < nd) {
@@ -83,152 +98,221 @@ __device__ __forceinline__ void adjoint_tile(const MllArgs& a, const ArchDev& ar
                 if (l < nd - 1) q = arch.act[l] == NNGP_ACT_ABRELU ? arch.ap[l][2] * qp : 0.5 * qp;
             }
         }
-    }
-
-    // ---- Gram tile: rows i0 + tr + 16 p, columns j0 + tc + 16 q, features summed in order ----
-    double (*s1)[MLD] = reinterpret_cast<double (*)[MLD]>(sm);
-    double (*s2)[MLD] = reinterpret_cast<double (*)[MLD]>(sm + MT * MLD);
-    double acc[4][4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc[p][q] = 0.0;
-    for (int k0 = 0; k0 < a.d; k0 += MKC) {
-        const int kc = a.d - k0 < MKC ? a.d - k0 : MKC;
-        for (int e = tid; e < MT * MKC; e += 256) {
-            const int r = e / MKC, k = e % MKC;
-            const int64_t i = i0 + r, j = j0 + r;
-            s1[r][k] = (k < kc && i < a.n) ? a.x[i * a.d + k0 + k] : 0.0;
-            s2[r][k] = (k < kc && j < a.n) ? a.x[j * a.d + k0 + k] : 0.0;
-        }
-        __syncthreads();
-        for (int k = 0; k < kc; ++k) {
-            double u[4], v[4];
-#pragma unroll
-            for (int p = 0; p < 4; ++p) u[p] = s1[tr + 16 * p][k];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) v[q] = s2[tc + 16 * q][k];
-#pragma unroll
-            for (int p = 0; p < 4; ++p)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[p][q] = fma(u[p], v[q], acc[p][q]);
-        }
-        __syncthreads();
-    }
-    double (*gt)[MT + 1] = reinterpret_cast<double (*)[MT + 1]>(sm);
-    const double inv_d = 1.0 / (double)a.d;
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) gt[tr + 16 * p][tc + 16 * q] = acc[p][q] * inv_d;
-    __syncthreads();
-
-    // ---- per entry: forward recursion, then the adjoint sweep from both seeds ----
+    };
     double ga[2 * NLC], gi[2 * NLC];
+    const int n_terms = ADD ? add.n_terms : 1;
+    int t = 0;
+    do {  // the terms; a do loop, with which the plain instantiations compile to the registers they had without it
+        const bool grp = ADD && t > 0;  // a group's term: the slice's own q, the identical-slice rule
+        int kb = 0, ke = a.d;
+        [[maybe_unused]] double wt = 1.0;
+        if constexpr (ADD) {
+            wt = add.tw[t];
+            if (grp) {
+                kb = add.gbegin[t - 1];
+                ke = add.gend[t - 1];
+            }
+        }
+        if (!grp && tid < 2 * MT) {
+            const int64_t g = tid < MT ? i0 + tid : j0 + tid - MT;
+            q_chain(g < a.n ? a.q[g] : 0.0);
+        }
+
+        // ---- Gram tile: rows i0 + tr + 16 p, columns j0 + tc + 16 q, features summed in order ----
+        double (*s1)[MLD] = reinterpret_cast<double (*)[MLD]>(sm);
+        double (*s2)[MLD] = reinterpret_cast<double (*)[MLD]>(sm + MT * MLD);
+        double acc[4][4];
+        [[maybe_unused]] double qa[ADD ? 4 : 1], qb[ADD ? 4 : 1];
 #pragma unroll
-    for (int c = 0; c < 2 * NLC; ++c) ga[c] = gi[c] = 0.0;
-#pragma unroll 1
-    for (int e = 0; e < 16; ++e) {
-        const int ri = tr + 16 * (e >> 2), cj = tc + 16 * (e & 3);
-        const int64_t i = i0 + ri, j = j0 + cj;
-        if (i >= a.n || j > i) continue;  // padding, and the upper half of a diagonal tile (j <= i < n for every other entry)
-        const bool dg = i == j;
-        const double w = dg ? 1.0 : 2.0;  // the lower triangle stands for the whole square
-        double kb_a;
-        if constexpr (LOO) kb_a = w * (0.5 * (a.alpha[i] * a.u[j] + a.u[i] * a.alpha[j]));
-        else kb_a = w * (a.alpha[i] * a.alpha[j]);
-        double kb_i = w * a.ainv[i * a.ld + j];
-        double k = dg ? qs[0][ri] : gt[ri][cj];  // exact diagonal: q q' - k^2 == 0 holds exactly
-        double kin[NLC], ck[NLC], cs[NLC];  // per layer: k into Dense l; dK'/dk and (b - a)^2 s of the activation after it
+        for (int p = 0; p < 4; ++p)
 #pragma unroll
-        for (int l = 0; l < NLC; ++l) {
-            kin[l] = k;
-            ck[l] = 0.0;
-            cs[l] = 0.0;
-            if (l < nd - 1) {
-                const double v = arch.w2[l], c = arch.b2[l];
-                const bool ab = arch.act[l] == NNGP_ACT_ABRELU;
-                k = fma(v, k, c);
-                if (dg) {  // theta = 0: K' = (a^2 + b^2) / 2 k  (1/2 for ReLU), no q dependence
-                    const double kd = ab ? arch.ap[l][2] : 0.5;
-                    k *= kd;
-                    ck[l] = kd;
-                } else {
-                    const double q1 = fma(v, qs[l][ri], c), q2 = fma(v, qs[l][MT + cj], c);
-                    const double rr = fma(q1, q2, -k * k);
-                    const double s = rr > 0.0 ? fast_sqrt_pos(rr > 0.0 ? rr : 1.0) : 0.0;
-                    const double kr = pi_minus_atan2(s, k, tab) * (0.5 / kPi);  // kdot
-                    const double kk = fma(kr, k, s * (0.5 / kPi));
-                    if (ab) {
-                        k = fma(arch.ap[l][0], k, arch.ap[l][1] * kk);
-                        ck[l] = fma(arch.ap[l][1], kr, arch.ap[l][0]);
-                        cs[l] = arch.ap[l][1] * s;
-                    } else {
-                        k = kk;
-                        ck[l] = kr;
-                        cs[l] = s;
+            for (int q = 0; q < 4; ++q) acc[p][q] = 0.0;
+        if constexpr (ADD) {
+#pragma unroll
+            for (int p = 0; p < 4; ++p) qa[p] = qb[p] = 0.0;
+        }
+        for (int k0 = kb; k0 < ke; k0 += MKC) {
+            const int kc = ke - k0 < MKC ? ke - k0 : MKC;
+            for (int e = tid; e < MT * MKC; e += 256) {
+                const int r = e / MKC, k = e % MKC;
+                const int64_t i = i0 + r, j = j0 + r;
+                s1[r][k] = (k < kc && i < a.n) ? a.x[i * a.d + k0 + k] : 0.0;
+                s2[r][k] = (k < kc && j < a.n) ? a.x[j * a.d + k0 + k] : 0.0;
+            }
+            __syncthreads();
+            for (int k = 0; k < kc; ++k) {
+                double u[4], v[4];
+#pragma unroll
+                for (int p = 0; p < 4; ++p) u[p] = s1[tr + 16 * p][k];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) v[q] = s2[tc + 16 * q][k];
+#pragma unroll
+                for (int p = 0; p < 4; ++p)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) acc[p][q] = fma(u[p], v[q], acc[p][q]);
+                if constexpr (ADD) {
+#pragma unroll
+                    for (int p = 0; p < 4; ++p) {
+                        qa[p] = fma(u[p], u[p], qa[p]);
+                        qb[p] = fma(v[p], v[p], qb[p]);
                     }
                 }
             }
+            __syncthreads();
         }
-        double q1a = 0.0, q2a = 0.0, q1i = 0.0, q2i = 0.0;
+        double (*gt)[MT + 1] = reinterpret_cast<double (*)[MT + 1]>(sm);
+        const double inv_d = 1.0 / (double)(ke - kb);
 #pragma unroll
-        for (int l = NLC - 1; l >= 0; --l) {
-            if (l < nd) {
-                if (l < nd - 1) {  // the activation after Dense layer l: dK'/dq1 = (b - a)^2 s / (4 pi q1'), q' = h q
-                    const double h = arch.act[l] == NNGP_ACT_ABRELU ? arch.ap[l][2] : 0.5;
-                    const double t1 = cs[l] * rq[l][ri], t2 = cs[l] * rq[l][MT + cj];
-                    q1a = fma(kb_a, t1, h * q1a);
-                    q2a = fma(kb_a, t2, h * q2a);
-                    kb_a *= ck[l];
-                    q1i = fma(kb_i, t1, h * q1i);
-                    q2i = fma(kb_i, t2, h * q2i);
-                    kb_i *= ck[l];
+        for (int p = 0; p < 4; ++p)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) gt[tr + 16 * p][tc + 16 * q] = acc[p][q] * inv_d;
+        if constexpr (ADD) {
+            if (grp) {  // every row / column of the tile has 16 threads with the same sums: one of them writes
+#pragma unroll
+                for (int p = 0; p < 4; ++p) {
+                    if (tc == 0) qg[tr + 16 * p] = qa[p] * inv_d;
+                    if (tr == 0) qg[MT + tc + 16 * p] = qb[p] * inv_d;
                 }
-                // Dense layer l: k' = v k + c (likewise q1, q2)
-                const double v = arch.w2[l], x1 = qs[l][ri], x2 = qs[l][MT + cj];
-                ga[2 * l] += fma(kb_a, kin[l], fma(q1a, x1, q2a * x2));
-                ga[2 * l + 1] += kb_a + q1a + q2a;
-                gi[2 * l] += fma(kb_i, kin[l], fma(q1i, x1, q2i * x2));
-                gi[2 * l + 1] += kb_i + q1i + q2i;
-                kb_a *= v;
-                q1a *= v;
-                q2a *= v;
-                kb_i *= v;
-                q1i *= v;
-                q2i *= v;
+            }
+        }
+        __syncthreads();
+        if constexpr (ADD) {
+            if (grp) {
+                if (tid < 2 * MT) q_chain(qg[tid]);
+                __syncthreads();
+            }
+        }
+
+        // ---- per entry: forward recursion, then the adjoint sweep from both seeds ----
+        if (t == 0) {  // the accumulators are shared by all terms
+#pragma unroll
+            for (int c = 0; c < 2 * NLC; ++c) ga[c] = gi[c] = 0.0;
+        }
+        [[maybe_unused]] double ha = 0.0, hi = 0.0;  // ADD: the term's value against either seed
+#pragma unroll 1
+        for (int e = 0; e < 16; ++e) {
+            const int ri = tr + 16 * (e >> 2), cj = tc + 16 * (e & 3);
+            const int64_t i = i0 + ri, j = j0 + cj;
+            if (i >= a.n || j > i) continue;  // padding, and the upper half of a diagonal tile (j <= i < n for every other entry)
+            // a group's term takes the diagonal form wherever both slices give k == q == q' bit for bit (the diagonal does)
+            const bool dg = grp ? (qs[0][ri] == gt[ri][cj] && qs[0][MT + cj] == gt[ri][cj]) : i == j;
+            const double w = i == j ? 1.0 : 2.0;  // the lower triangle stands for the whole square
+            double kb_a;
+            if constexpr (LOO) kb_a = w * (0.5 * (a.alpha[i] * a.u[j] + a.u[i] * a.alpha[j]));
+            else kb_a = w * (a.alpha[i] * a.alpha[j]);
+            double kb_i = w * a.ainv[i * a.ld + j];
+            double k = dg ? qs[0][ri] : gt[ri][cj];  // exact diagonal: q q' - k^2 == 0 holds exactly
+            double kin[NLC], ck[NLC], cs[NLC];  // per layer: k into Dense l; dK'/dk and (b - a)^2 s of the activation after it
+#pragma unroll
+            for (int l = 0; l < NLC; ++l) {
+                kin[l] = k;
+                ck[l] = 0.0;
+                cs[l] = 0.0;
+                if constexpr (ADD) {
+                    if (l == nd - 1) {  // K^(t)_ij, out of the last Dense layer
+                        const double val = fma(arch.w2[l], k, arch.b2[l]);
+                        ha = fma(kb_a, val, ha);
+                        hi = fma(kb_i, val, hi);
+                    }
+                }
+                if (l < nd - 1) {
+                    const double v = arch.w2[l], c = arch.b2[l];
+                    const bool ab = arch.act[l] == NNGP_ACT_ABRELU;
+                    k = fma(v, k, c);
+                    if (dg) {  // theta = 0: K' = (a^2 + b^2) / 2 k  (1/2 for ReLU), no q dependence
+                        const double kd = ab ? arch.ap[l][2] : 0.5;
+                        k *= kd;
+                        ck[l] = kd;
+                    } else {
+                        const double q1 = fma(v, qs[l][ri], c), q2 = fma(v, qs[l][MT + cj], c);
+                        const double rr = fma(q1, q2, -k * k);
+                        const double s = rr > 0.0 ? fast_sqrt_pos(rr > 0.0 ? rr : 1.0) : 0.0;
+                        const double kr = pi_minus_atan2(s, k, tab) * (0.5 / kPi);  // kdot
+                        const double kk = fma(kr, k, s * (0.5 / kPi));
+                        if (ab) {
+                            k = fma(arch.ap[l][0], k, arch.ap[l][1] * kk);
+                            ck[l] = fma(arch.ap[l][1], kr, arch.ap[l][0]);
+                            cs[l] = arch.ap[l][1] * s;
+                        } else {
+                            k = kk;
+                            ck[l] = kr;
+                            cs[l] = s;
+                        }
+                    }
+                }
+            }
+            if constexpr (ADD) {
+                if (wt == 0.0) continue;  // the term is not in K: its own d/dw_t only
+                kb_a *= wt;
+                kb_i *= wt;
+            }
+            double q1a = 0.0, q2a = 0.0, q1i = 0.0, q2i = 0.0;
+#pragma unroll
+            for (int l = NLC - 1; l >= 0; --l) {
+                if (l < nd) {
+                    if (l < nd - 1) {  // the activation after Dense layer l: dK'/dq1 = (b - a)^2 s / (4 pi q1'), q' = h q
+                        const double h = arch.act[l] == NNGP_ACT_ABRELU ? arch.ap[l][2] : 0.5;
+                        const double t1 = cs[l] * rq[l][ri], t2 = cs[l] * rq[l][MT + cj];
+                        q1a = fma(kb_a, t1, h * q1a);
+                        q2a = fma(kb_a, t2, h * q2a);
+                        kb_a *= ck[l];
+                        q1i = fma(kb_i, t1, h * q1i);
+                        q2i = fma(kb_i, t2, h * q2i);
+                        kb_i *= ck[l];
+                    }
+                    // Dense layer l: k' = v k + c (likewise q1, q2)
+                    const double v = arch.w2[l], x1 = qs[l][ri], x2 = qs[l][MT + cj];
+                    ga[2 * l] += fma(kb_a, kin[l], fma(q1a, x1, q2a * x2));
+                    ga[2 * l + 1] += kb_a + q1a + q2a;
+                    gi[2 * l] += fma(kb_i, kin[l], fma(q1i, x1, q2i * x2));
+                    gi[2 * l + 1] += kb_i + q1i + q2i;
+                    kb_a *= v;
+                    q1a *= v;
+                    q2a *= v;
+                    kb_i *= v;
+                    q1i *= v;
+                    q2i *= v;
+                }
+            }
+            if constexpr (ARD) {
+                if (dg) {
+                    rsum[0][ri][tc] += kb_a;
+                    rsum[1][ri][tc] += kb_i;
+                } else {
+                    a.cmat[i * a.ldc + j] = kb_a;
+                    a.cmat[j * a.ldc + i] = kb_i;
+                    rsum[0][ri][tc] += q1a;
+                    rsum[1][ri][tc] += q1i;
+                    csum[0][cj][tr] += q2a;
+                    csum[1][cj][tr] += q2i;
+                }
             }
         }
         if constexpr (ARD) {
-            if (dg) {
-                rsum[0][ri][tc] += kb_a;
-                rsum[1][ri][tc] += kb_i;
+            __syncthreads();
+            const int arr = tid >> 6, r = tid & (MT - 1);  // 0, 1: row sums of seed 0, 1; 2, 3: column sums
+            const double* src = arr < 2 ? rsum[arr][r] : csum[arr - 2][r];
+            double t = 0.0;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) t += src[e];
+            red[tid] = t;
+            __syncthreads();
+            if (ti == tj) {
+                if (tid < 2 * MT) a.qbar[((int64_t)arr * tn + ti) * a.np + i0 + r] = red[tid] + red[tid + 2 * MT];
             } else {
-                a.cmat[i * a.ldc + j] = kb_a;
-                a.cmat[j * a.ldc + i] = kb_i;
-                rsum[0][ri][tc] += q1a;
-                rsum[1][ri][tc] += q1i;
-                csum[0][cj][tr] += q2a;
-                csum[1][cj][tr] += q2i;
+                a.qbar[((int64_t)(arr & 1) * tn + (arr < 2 ? tj : ti)) * a.np + (arr < 2 ? i0 : j0) + r] = t;
+            }
+            __syncthreads();
+        }
+        if constexpr (ADD) {  // the term's halves, one slot per (term, tile); the barriers also free the panels for the next term
+            const double ra = block_sum(ha, red);
+            const double rb = block_sum(hi, red);
+            if (tid == 0) {
+                add.tpart[(int64_t)(2 * t) * a.nparts + blockIdx.x] = ra;
+                add.tpart[(int64_t)(2 * t + 1) * a.nparts + blockIdx.x] = rb;
             }
         }
-    }
-    if constexpr (ARD) {
-        __syncthreads();
-        const int arr = tid >> 6, r = tid & (MT - 1);  // 0, 1: row sums of seed 0, 1; 2, 3: column sums
-        const double* src = arr < 2 ? rsum[arr][r] : csum[arr - 2][r];
-        double t = 0.0;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) t += src[e];
-        red[tid] = t;
-        __syncthreads();
-        if (ti == tj) {
-            if (tid < 2 * MT) a.qbar[((int64_t)arr * tn + ti) * a.np + i0 + r] = red[tid] + red[tid + 2 * MT];
-        } else {
-            a.qbar[((int64_t)(arr & 1) * tn + (arr < 2 ? tj : ti)) * a.np + (arr < 2 ? i0 : j0) + r] = t;
-        }
-        __syncthreads();
-    }
+    } while (ADD && ++t < n_terms);
     const int ncomp = 2 * nd;
 #pragma unroll
     for (int c = 0; c < 2 * NLC; ++c) {
@@ -245,13 +329,15 @@ __device__ __forceinline__ void adjoint_tile(const MllArgs& a, const ArchDev& ar
 
 // out[e] = sum_i q_i^(e), the diagonal's q at the input of Dense layer e (one workgroup, fixed order): tr dK/dtheta follows from
 // these in closed form (trace_dk)
-__device__ __forceinline__ void finish_qsums(const double* q, int64_t n, const ArchDev& arch, double* red, double* out) {
+// q_of(i): the diagonal's q at the input of Dense layer 0
+template <class Q>
+__device__ __forceinline__ void finish_qsums_of(Q q_of, int64_t n, const ArchDev& arch, double* red, double* out) {
     const int nd = arch.n_dense;
     double sq[NNGP_MAX_DENSE];
 #pragma unroll
     for (int e = 0; e < NNGP_MAX_DENSE; ++e) sq[e] = 0.0;
     for (int64_t i = threadIdx.x; i < n; i += 256) {
-        double z = q[i];
+        double z = q_of(i);
 #pragma unroll
         for (int e = 0; e < NNGP_MAX_DENSE; ++e) {
             if (e < nd) {
@@ -268,6 +354,10 @@ __device__ __forceinline__ void finish_qsums(const double* q, int64_t n, const A
             if (threadIdx.x == 0) out[e] = r;
         }
     }
+}
+
+__device__ __forceinline__ void finish_qsums(const double* q, int64_t n, const ArchDev& arch, double* red, double* out) {
+    finish_qsums_of([q](int64_t i) { return q[i]; }, n, arch, red, out);
 }
 
 // tr dK / dtheta from the diagonal's closed form: K_ii = u_{nd-1}, u_l = v_l z_l + c_l, z_{l+1} = h_l u_l, so
@@ -299,6 +389,19 @@ struct ArdBuffers {
     std::vector<double> terms;  // nngp_mll_ard_terms: both halves per feature, then tr dK/ds_k
     bool have_terms = false;
 };
+// What nngp_mll_reserve_additive adds to the handle (include/nngp_additive_mll.h); empty on a handle without a group table
+struct AddBuffers {
+    bool reserved = false;
+    int n_terms = 0;              // T = 1 + n_groups, zero-weight groups included
+    int* range = nullptr;         // device [4 G]: begin, end of every group; then begin, end of the groups with w_g > 0 (the build's)
+    double* weight = nullptr;     // device [T + G]: w0, w_g; then the w_g > 0 (the build's table)
+    double* red = nullptr;        // device [T (2 + NNGP_MAX_DENSE)]: the term halves summed over the tiles, then per term sum_i z_l,i
+    GroupsDev dev{};              // the build's table of the current evaluation (points into range / weight)
+    std::vector<int> range_host;
+    std::vector<double> weight_host, red_host;
+    std::vector<double> terms;    // nngp_mll_additive_terms
+    bool have_terms = false;
+};
 }  // namespace nngp
 
 // The handle of include/nngp_mll.h, include/nngp_loo.h and include/nngp_ard.h
@@ -315,6 +418,7 @@ struct nngp_mll {
     double loo_terms[2 * (nngp::kMaxComp + 1) + 3 + nngp::kMaxComp] = {};
     int n_loo_terms = 0;
     nngp::ArdBuffers ard;
+    nngp::AddBuffers add;
 };
 
 namespace nngp {
@@ -326,8 +430,11 @@ int mll_build_a(nngp_mll* h, const ArchDev& arch, int get, double diag_reg, int 
                 hipStream_t s);
 // The evaluations behind nngp_mll_evaluate / nngp_mll_loo_evaluate and their _ard forms.  rel: host, d relevances, or NULL for
 // the handle's own x (then grad_s is NULL too); grad_s: host, d values, or NULL.
+// weights: host, the 1 + n_groups term weights of the additive kernel (then rel is NULL), or NULL for the plain kernel; grad_w: host,
+// as many values, or NULL.
 int mll_evaluate_core(nngp_mll* h, const nngp_arch_act* arch_in, double diag_reg, int absolute, double* nlml, double* grad,
-                      const double* rel, double* grad_s, const char* who, hipStream_t s);
+                      const double* rel, double* grad_s, const char* who, hipStream_t s, const double* weights = nullptr,
+                      double* grad_w = nullptr);
 int loo_evaluate_core(nngp_mll* h, const nngp_arch_act* arch_in, int get, double diag_reg, int absolute, int objective, double* value,
                       double* grad, const double* rel, double* grad_s, const char* who, hipStream_t s);
 // nngp_ard.hip.  ard_begin: checks rel, uploads it, fills ard.xs and ard.q.  launch_ard_partial: the adjoint pass with ARD set
@@ -339,4 +446,15 @@ int launch_ard_partial(nngp_mll* h, MllArgs a, const ArchDev& arch, bool loo, hi
 int ard_contract(nngp_mll* h, hipStream_t s);
 void ard_finish_host(nngp_mll* h, const ArchDev& arch, double diag_reg, int absolute, double s1, double s2, bool loo, double* grad_s);
 void ard_free(nngp_mll* h);
+// nngp_mll_additive.hip.  add_begin: checks the weights, uploads them and the build's table; *groups is that table, or NULL when
+// it is the plain kernel (no group, w0 = 1).  launch_add_partial: the adjoint pass with ADD set, its term partials over L^-T.
+// launch_add_finish: the fixed-order sums of the plain finish kernel (their bits) and of the term partials, over several
+// workgroups, and the per-term sums of the diagonal's q chain; queues the host copy.  add_trace_dk (after the stream is
+// synchronised): tr dK/dtheta_p = sum_t w_t tr dK^(t)/dtheta_p.  add_finish_host: grad_w and the terms; aa = alpha^T alpha.
+int add_begin(nngp_mll* h, const double* weights, const char* who, const GroupsDev** groups, hipStream_t s);
+int launch_add_partial(nngp_mll* h, const MllArgs& a, const ArchDev& arch, hipStream_t s);
+int launch_add_finish(nngp_mll* h, const ArchDev& arch, int64_t nparts, hipStream_t s);
+void add_trace_dk(const nngp_mll* h, const ArchDev& arch, double dn, double* trdk);
+void add_finish_host(nngp_mll* h, const ArchDev& arch, double diag_reg, int absolute, double aa, double tr_ainv, double* grad_w);
+void add_free(nngp_mll* h);
 }  // namespace nngp

@@ -121,6 +121,8 @@ extern "C" {
 
 int nngp_mll_reserve_ard(nngp_mll* h) {
     NNGP_REQUIRE(h != nullptr, "mll_reserve_ard: NULL argument");
+    NNGP_REQUIRE(!h->add.reserved, "mll_reserve_ard: the handle has a group table (nngp_mll_reserve_additive); relevances together "
+                                   "with groups are not covered");
     ArdBuffers& a = h->ard;
     if (a.reserved) return 0;
     const GpWorkspace& w = h->w;

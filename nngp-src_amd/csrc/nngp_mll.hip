@@ -117,20 +117,21 @@ int mll_build_a(nngp_mll* h, const ArchDev& arch, int get, double diag_reg, int 
 }
 
 int mll_evaluate_core(nngp_mll* h, const nngp_arch_act* arch_in, double diag_reg, int absolute, double* nlml, double* grad,
-                      const double* rel, double* grad_s, const char* who, hipStream_t s) {
+                      const double* rel, double* grad_s, const char* who, hipStream_t s, const double* weights, double* grad_w) {
     NNGP_REQUIRE(h != nullptr && arch_in != nullptr && nlml != nullptr, "%s: NULL argument", who);
     NNGP_REQUIRE(h->w.n > 0, "%s: no training data (nngp_mll_set_train)", who);
     ArchDev arch{};
     NNGP_TRY(mll_make_arch(arch_in, diag_reg, who, &arch));
     const int nd = arch.n_dense;
     GpWorkspace& w = h->w;
-    w.factored = h->have_terms = h->ard.have_terms = false;
+    w.factored = h->have_terms = h->ard.have_terms = h->add.have_terms = false;
     const int64_t n = w.n, np = w.np;
     if (rel) NNGP_TRY(ard_begin(h, rel, who, s));
+    if (weights) NNGP_TRY(add_begin(h, weights, who, &arch.groups, s));
     const double* x = rel ? h->ard.xs : w.x;
     const double* q = rel ? h->ard.q : h->q;
     NNGP_TRY(mll_build_a(h, arch, NNGP_GET_NNGP, diag_reg, absolute, x, q, s));
-    const bool want = grad != nullptr || grad_s != nullptr;
+    const bool want = grad != nullptr || grad_s != nullptr || grad_w != nullptr;
     double own_grad[kMaxComp + 1];
     if (want && !grad) grad = own_grad;
     NNGP_TRY(factor_and_solve(&w, want, who, s));
@@ -138,11 +139,16 @@ int mll_evaluate_core(nngp_mll* h, const nngp_arch_act* arch_in, double diag_reg
     if (want) {
         MllArgs ma{x, q, n, w.d, w.ainv, np, w.alpha, nullptr, w.part, nparts};
         if (grad_s) NNGP_TRY(launch_ard_partial(h, ma, arch, false, s));  // L^-T is dead: the seeded adjoints go over it
+        else if (weights) NNGP_TRY(launch_add_partial(h, ma, arch, s));     // and so do the term partials
         else NNGP_TRY(launch_mll_partial(ma, arch, s));
     }
-    hipLaunchKernelGGL(k_mll_finish, dim3(1), dim3(256), 0, s, w.a, np, n, w.wrow, want ? w.part : nullptr, nparts,
-                       want ? w.alpha : nullptr, w.ainv, q, arch, w.red + kRed);
-    NNGP_HIP_CHECK(hipGetLastError());
+    if (want && weights) {
+        NNGP_TRY(launch_add_finish(h, arch, nparts, s));
+    } else {
+        hipLaunchKernelGGL(k_mll_finish, dim3(1), dim3(256), 0, s, w.a, np, n, w.wrow, want ? w.part : nullptr, nparts,
+                           want ? w.alpha : nullptr, w.ainv, q, arch, w.red + kRed);
+        NNGP_HIP_CHECK(hipGetLastError());
+    }
     if (grad_s) NNGP_TRY(ard_contract(h, s));
     double r[kRedLen];
     NNGP_HIP_CHECK(hipMemcpyAsync(r, w.red, sizeof(r), hipMemcpyDeviceToHost, s));
@@ -159,7 +165,8 @@ int mll_evaluate_core(nngp_mll* h, const nngp_arch_act* arch_in, double diag_reg
     const double* pi = pa + 2 * nd;     // A^-1 halves
     const int ncomp = 2 * nd;
     double trdk[kMaxComp];
-    trace_dk(arch, sq, dn, trdk);
+    if (weights) add_trace_dk(h, arch, dn, trdk);
+    else trace_dk(arch, sq, dn, trdk);
     double* t = h->terms;
     for (int p = 0; p <= ncomp; ++p) {
         double qa, ta;  // alpha^T dA_p alpha, tr(A^-1 dA_p)
@@ -186,6 +193,7 @@ int mll_evaluate_core(nngp_mll* h, const nngp_arch_act* arch_in, double diag_reg
     h->n_terms = 2 * (ncomp + 1) + 5 + ncomp;
     h->have_terms = true;
     if (grad_s) ard_finish_host(h, arch, diag_reg, absolute, aa, tr_ainv, false, grad_s);
+    if (grad_w) add_finish_host(h, arch, diag_reg, absolute, aa, tr_ainv, grad_w);
     return 0;
 }
 
@@ -198,6 +206,7 @@ using namespace nngp;
 
 static void mll_free(nngp_mll* h) {
     ard_free(h);
+    add_free(h);
     dev_free(h->q);
     dev_free(h->loo);
     ws_free(&h->w);

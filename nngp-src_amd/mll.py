@@ -32,10 +32,12 @@ def _arch_of(kernel_fn_or_params):
 
 def reject_groups(kernel_fn_or_params, what):
     """ValueError for a kernel_fn that carries feature groups (stax.additive): the evidence and leave-one-out passes build the
-    plain kernel, and the gradient with respect to the group weights does not exist yet."""
+    plain kernel (additive_mll.py has the additive kernel's evidence and its gradient in the group weights)."""
     if KernelSpec.of(kernel_fn_or_params).groups is not None:
         raise ValueError("%s does not cover the additive kernel over feature groups (kernel_fn.groups is set): evaluate or "
-                         "tune the plain kernel_fn, then add the groups with kernel_fn.with_groups(...)" % what)
+                         "tune the plain kernel_fn, then add the groups with kernel_fn.with_groups(...); the marginal likelihood of the "
+                         "additive kernel itself, term weights included, is additive_mll.marginal_likelihood / "
+                         "additive_mll.tune_hyperparameters" % what)
 
 
 def check_supported(kernel_fn_or_params, get="nngp"):

@@ -57,7 +57,8 @@ def NNGP_train_and_test(args, X_train, Y_train, X_test, Y_test, query_infos_trai
 
     if kernel_fn is None:
         init_fn, apply_fn, kernel_fn = kernel_fn_from_args(args)
-    if getattr(args, "additive", "none") == "pairs":  # slot pairs + the whole input (tuning, above, is the plain kernel's)
+    # slot pairs + the whole input; --tune_additive has tuned the kernel with its groups and brings them along
+    if getattr(args, "additive", "none") == "pairs" and kernel_fn.groups is None:
         kernel_fn = kernel_fn.with_groups("pairs", full_weight=getattr(args, "additive_full_weight", 1.0))
     kernel_fn = batch(kernel_fn, device_count=0, batch_size=0)
     start = datetime.datetime.now()
@@ -136,6 +137,14 @@ def tune_kernel_fn(args, X_train, Y_train):
     from . import loo, mll
     _, _, kernel_fn = kernel_fn_from_args(args)
     objective = getattr(args, "tune_objective", "mll")
+    if getattr(args, "tune_additive", False):  # --tune_additive: the evidence of the additive kernel itself, its weights tuned too
+        from . import additive_mll
+        kernel_fn = kernel_fn.with_groups("pairs", full_weight=getattr(args, "additive_full_weight", 1.0))
+        kernel_fn, diag_reg, _ = additive_mll.tune_hyperparameters(kernel_fn, X_train, Y_train, diag_reg=1e-3, steps=args.tune_hyper,
+                                                                   lr=args.tune_lr, b_std_init=args.b_std_init)
+        print("Tuned W_std={} b_std={} diag_reg={}".format(list(kernel_fn.w_std), list(kernel_fn.b_std), diag_reg))
+        print("Tuned weights: full={} groups={}".format(kernel_fn.full_weight, list(kernel_fn.group_weights)))
+        return kernel_fn, diag_reg
     ard = {}
     if getattr(args, "tune_ard", False):  # --tune_ard: one relevance per input feature joins the tuned values (nngp_ard.h)
         groups = getattr(args, "ard_groups", "none")
@@ -231,7 +240,11 @@ def make_parser():
                         help="--tune_ard: 'pairs' ties features 2i and 2i+1, the two ends of a column's range")
     parser.add_argument("--additive", type=str, default="none", choices=("none", "pairs"),
                         help="'pairs': the additive kernel -- one network per column's (upper, lower) slot pair plus the whole input "
-                             "(--tune_hyper and --loo work on the plain kernel only)")
+                             "(--loo works on the plain kernel only; --tune_hyper tunes the plain kernel and adds the groups "
+                             "afterwards unless --tune_additive is given)")
+    parser.add_argument("--tune_additive", action='store_true',
+                        help="with --tune_hyper STEPS --additive pairs: tune on the evidence of the additive kernel itself, the "
+                             "term weights included (W_std of the last layer is then fixed)")
     parser.add_argument("--additive_full_weight", type=float, default=1.0,
                         help="--additive: weight of the whole-input term (0 leaves it out)")
     parser.add_argument("--sparse", type=int, default=0, metavar="M",
@@ -255,7 +268,8 @@ def make_parser():
 
 def parse_args(argv=None):
     """The command line with its conflicts checked: --sparse goes with --kernel_type nngp only, and not with --loo or --tune_*;
-    --sparse_tune needs --sparse, --sparse_tune_ard needs both."""
+    --sparse_tune needs --sparse, --sparse_tune_ard needs both; --tune_additive needs --tune_hyper, --additive pairs, the NNGP
+    and the marginal likelihood."""
     parser = make_parser()
     args = parser.parse_args(argv)
     if args.sparse < 0:
@@ -266,6 +280,10 @@ def parse_args(argv=None):
         parser.error("argument --sparse_tune_ard: needs --sparse M and --sparse_tune STEPS (it tunes relevances on the sparse evidence)")
     if args.sparse_tune > 0 and args.sparse <= 0:
         parser.error("argument --sparse_tune: needs --sparse M (it tunes the sparse model's evidence)")
+    if args.tune_additive and not (args.tune_hyper > 0 and args.additive == "pairs" and args.kernel_type == "nngp"
+                                   and args.tune_objective == "mll" and not args.tune_ard and args.sparse <= 0):
+        parser.error("argument --tune_additive: needs --tune_hyper STEPS, --additive pairs, --kernel_type nngp and "
+                     "--tune_objective mll (it tunes the additive kernel's marginal likelihood), without --tune_ard or --sparse")
     if args.sparse > 0:
         if args.kernel_type != "nngp":
             parser.error("argument --sparse: not allowed with --kernel_type %s (the sparse model is the NNGP posterior)" % args.kernel_type)
