@@ -81,6 +81,9 @@ SPARSE_ARD_ABI_SYMBOLS = ("nngp_sparse_reserve_ard", "nngp_sparse_set_relevance"
                           "nngp_sparse_ard_terms", "nngp_sparse_ard_rect")
 # include/nngp_i8s.h: the stand-alone operators of the sliced int8 product (cuts, residual, fused statistics); GPU library only
 I8S_ABI_SYMBOLS = ("nngp_i8s_cut_rows", "nngp_i8s_cut_sym", "nngp_i8s_residual")
+# include/nngp_matfree.h: the matrix-free exact NNGP posterior and its fused K.V operator; GPU library only (no host build)
+MATFREE_ABI_SYMBOLS = ("nngp_matfree_create", "nngp_matfree_destroy", "nngp_matfree_fit", "nngp_matfree_solve",
+                       "nngp_matfree_predict", "nngp_matfree_alpha", "nngp_matfree_info", "nngp_kmv_f64")
 BOUND_DTC, BOUND_VFE = 0, 1
 BOUNDS = {"dtc": BOUND_DTC, "vfe": BOUND_VFE}
 
@@ -110,6 +113,12 @@ class NngpFitInfo(ctypes.Structure):
 class NngpSparseInfo(ctypes.Structure):
     _fields_ = [("n", ctypes.c_int64), ("m", ctypes.c_int64), ("m_padded", ctypes.c_int64), ("chunks", ctypes.c_int64),
                 ("sigma2", ctypes.c_double), ("trace_mean", ctypes.c_double), ("jitter_added", ctypes.c_double)]
+
+
+class NngpMatfreeInfo(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_int64), ("m", ctypes.c_int64), ("sigma2", ctypes.c_double), ("iterations", ctypes.c_int32),
+                ("k_passes", ctypes.c_int32), ("rel_residual", ctypes.c_double), ("converged", ctypes.c_int32),
+                ("restarts", ctypes.c_int32)]
 
 
 class NngpError(RuntimeError):
@@ -151,6 +160,7 @@ def load(knobs: bool = False):
     bind_sparse_evidence_prototypes(lib)
     bind_sparse_ard_prototypes(lib)
     bind_i8s_prototypes(lib)
+    bind_matfree_prototypes(lib)
     _libs[knobs] = lib
     return lib
 
@@ -382,6 +392,24 @@ def bind_sparse_ard_prototypes(lib):
     lib.nngp_sparse_ard_terms.argtypes = [vp, pd, i32]
     lib.nngp_sparse_ard_rect.argtypes = [vp, i64, vp, i64, i32, archp, pd, vp, i64, vp, vp, pd, vp]
     for name in SPARSE_ARD_ABI_SYMBOLS:
+        getattr(lib, name).restype = ctypes.c_int
+    return lib
+
+
+def bind_matfree_prototypes(lib):
+    """Argument and result types of include/nngp_matfree.h (the HIP library only)."""
+    vp, i64, i32, dbl = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_double
+    archp = ctypes.POINTER(NngpArchAct)
+    lib.nngp_matfree_create.argtypes = [ctypes.POINTER(vp), i64, i64, i64, i64, i32, i32, archp, ctypes.POINTER(NngpGroups), i32, dbl,
+                                        i32, dbl]
+    lib.nngp_matfree_destroy.argtypes = [vp]
+    lib.nngp_matfree_fit.argtypes = [vp, vp, vp, i64, vp, i64, dbl, i32, vp]
+    lib.nngp_matfree_solve.argtypes = [vp, vp, i64, i32, vp, i64, dbl, i32, vp]
+    lib.nngp_matfree_predict.argtypes = [vp, vp, i64, i32, vp, vp, dbl, i32, vp]
+    lib.nngp_matfree_alpha.argtypes = [vp, vp, vp]
+    lib.nngp_matfree_info.argtypes = [vp, ctypes.POINTER(NngpMatfreeInfo)]
+    lib.nngp_kmv_f64.argtypes = [vp, i64, vp, i64, i32, vp, i64, i32, archp, dbl, vp]
+    for name in MATFREE_ABI_SYMBOLS:
         getattr(lib, name).restype = ctypes.c_int
     return lib
 

@@ -20,7 +20,7 @@ class Estimator(object):
     def __init__(self, schema_name: str, data_path: str, train_query_path: str, chunk_size: int = 64,
                  use_aux: bool = False, q_error_threshold: float = 100.0, coef_var_threshold: float = 1.0,
                  encoder=None, kernel_type: str = "nngp", serving: bool = True, groups=None, sparse: int = 0,
-                 sparse_select: str = "greedy"):
+                 sparse_select: str = "greedy", matrix_free: int = 0):
         self.schema_name = schema_name
         self.data_path = data_path
         self.train_query_path = train_query_path
@@ -30,6 +30,9 @@ class Estimator(object):
         self.sparse, self.sparse_select = int(sparse), sparse_select  # sparse > 0: serve from the inducing-point model (sparse.py)
         if self.sparse > 0 and kernel_type != "nngp":
             raise ValueError("sparse > 0 serves the NNGP posterior: it needs kernel_type='nngp'")
+        self.matrix_free = int(matrix_free)  # matrix_free = M > 0: the exact posterior by PCG with M inducing rows as preconditioner (matfree.py)
+        if self.matrix_free > 0 and (self.sparse > 0 or kernel_type != "nngp" or groups is not None):
+            raise ValueError("matrix_free > 0 solves the plain NNGP posterior: it needs kernel_type='nngp', no groups, and not sparse")
         self.serving = serving  # load_model also builds the explicit float64 inverse: predict = one product per batch
         print("loading schema and training data ... This may take seconds ...")
         if encoder is None:
@@ -51,7 +54,10 @@ class Estimator(object):
         if groups is not None:
             kernel_fn = kernel_fn.with_groups(groups)
         kernel_fn = batch(kernel_fn, device_count=0, batch_size=0)
-        if self.sparse > 0:  # fitted here: every training row through the accumulation, once
+        if self.matrix_free > 0:  # fitted here: the preconditioner's sparse fit, then alpha by PCG
+            from .matfree import matfree_mse_ensemble
+            self.predict_fn = matfree_mse_ensemble(kernel_fn, self.X_train, self.Y_train, self.matrix_free, diag_reg=1e-3)
+        elif self.sparse > 0:  # fitted here: every training row through the accumulation, once
             from .sparse import sparse_mse_ensemble
             self.predict_fn = sparse_mse_ensemble(kernel_fn, self.X_train, self.Y_train, self.sparse, diag_reg=1e-3,
                                                   select=self.sparse_select)
@@ -60,7 +66,7 @@ class Estimator(object):
 
     def load_model(self):
         model = self.predict_fn.model_for(self.kernel_type)  # kernel build + Cholesky + alpha, cached in HBM
-        if self.serving and self.sparse <= 0:
+        if self.serving and self.sparse <= 0 and self.matrix_free <= 0:
             model.prepare_serving()
         n = self.X_train.shape[0]
         print((n, model.ny), (n, n))  # the shapes the reference prints (estimator.py:39)

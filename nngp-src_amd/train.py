@@ -62,7 +62,14 @@ def NNGP_train_and_test(args, X_train, Y_train, X_test, Y_test, query_infos_trai
         kernel_fn = kernel_fn.with_groups("pairs", full_weight=getattr(args, "additive_full_weight", 1.0))
     kernel_fn = batch(kernel_fn, device_count=0, batch_size=0)
     start = datetime.datetime.now()
-    if (getattr(args, "sparse", 0) or 0) > 0:  # --sparse M: every training row, M inducing rows (sparse.py)
+    if (getattr(args, "matrix_free", 0) or 0) > 0:  # --matrix_free M: the exact posterior by PCG, M inducing rows as preconditioner
+        from .matfree import matfree_mse_ensemble
+        if args.kernel_type != "nngp":
+            raise ValueError("--matrix_free solves the NNGP posterior: it needs --kernel_type nngp")
+        predict_fn = matfree_mse_ensemble(kernel_fn, X_train, Y_train, args.matrix_free, diag_reg=diag_reg,
+                                          tol=getattr(args, "matrix_free_tol", 1e-10), max_iter=getattr(args, "matrix_free_iters", 1000),
+                                          chunk_rows=getattr(args, "sparse_chunk", 8192), jitter=getattr(args, "sparse_jitter", 1e-8))
+    elif (getattr(args, "sparse", 0) or 0) > 0:  # --sparse M: every training row, M inducing rows (sparse.py)
         from .sparse import sparse_mse_ensemble
         if args.kernel_type != "nngp":
             raise ValueError("--sparse serves the NNGP posterior: it needs --kernel_type nngp")
@@ -75,6 +82,8 @@ def NNGP_train_and_test(args, X_train, Y_train, X_test, Y_test, query_infos_trai
     print('Kernel construction in %s seconds.' % duration)
 
     cov_mode = True if getattr(args, "full_cov", False) else "diag"
+    if (getattr(args, "matrix_free", 0) or 0) > 0 and cov_mode is True:
+        raise ValueError("--matrix_free gives variances only: not with --full_cov")
     pred_mean, pred_cov = prediction(predict_fn, X_test, kernel_type=args.kernel_type, compute_cov=cov_mode)
     pred_std = np.sqrt(np.diag(pred_cov)) if cov_mode is True else np.sqrt(pred_cov)
 
@@ -261,13 +270,20 @@ def make_parser():
     parser.add_argument("--sparse_tune_ard", action='store_true',
                         help="with --sparse M --sparse_tune STEPS: also tune one relevance per input feature on the sparse evidence "
                              "(--ard_groups ties them; W_std of the first layer is fixed during the run)")
+    parser.add_argument("--matrix_free", type=int, default=0, metavar="M",
+                        help="the exact NNGP posterior without the N x N kernel: preconditioned CG over a fused K.V kernel, with the "
+                             "sparse model of M inducing rows as preconditioner (nngp only; 0: off)")
+    parser.add_argument("--matrix_free_tol", type=float, default=1e-10, metavar="T",
+                        help="--matrix_free: relative residual every solve must reach")
+    parser.add_argument("--matrix_free_iters", type=int, default=1000, metavar="K", help="--matrix_free: iteration limit of a solve")
     parser.add_argument("--tune_lr", type=float, default=0.05, help="step size of --tune_hyper")
     parser.add_argument("--b_std_init", type=float, default=None, help="start of b_std for layers with b_std = 0 (--tune_hyper)")
     return parser
 
 
 def parse_args(argv=None):
-    """The command line with its conflicts checked: --sparse goes with --kernel_type nngp only, and not with --loo or --tune_*;
+    """The command line with its conflicts checked: --matrix_free goes with --kernel_type nngp only, and not with --sparse, --loo,
+    --tune_*, --additive or --full_cov; --sparse goes with --kernel_type nngp only, and not with --loo or --tune_*;
     --sparse_tune needs --sparse, --sparse_tune_ard needs both; --tune_additive needs --tune_hyper, --additive pairs, the NNGP
     and the marginal likelihood."""
     parser = make_parser()
@@ -293,6 +309,23 @@ def parse_args(argv=None):
             parser.error("argument --sparse: not allowed with argument --tune_hyper / --tune_ard")
         if args.sparse_chunk < 128 or args.sparse_chunk % 128 != 0:
             parser.error("argument --sparse_chunk: must be a positive multiple of 128")
+    if args.matrix_free < 0:
+        parser.error("argument --matrix_free: M must be >= 0")
+    if args.matrix_free > 0:
+        if args.sparse > 0:
+            parser.error("argument --matrix_free: not allowed with argument --sparse")
+        if args.kernel_type != "nngp":
+            parser.error("argument --matrix_free: not allowed with --kernel_type %s (it solves the NNGP posterior)" % args.kernel_type)
+        if args.loo:
+            parser.error("argument --matrix_free: not allowed with argument --loo")
+        if args.tune_hyper or args.tune_ard or args.tune_additive:
+            parser.error("argument --matrix_free: not allowed with argument --tune_hyper / --tune_ard / --tune_additive")
+        if args.additive != "none":
+            parser.error("argument --matrix_free: not allowed with argument --additive (the fused operator has the plain kernel only)")
+        if args.full_cov:
+            parser.error("argument --matrix_free: not allowed with argument --full_cov (variances only)")
+        if not (0.0 < args.matrix_free_tol < 1.0) or args.matrix_free_iters < 1:
+            parser.error("argument --matrix_free_tol / --matrix_free_iters: need 0 < T < 1 and K >= 1")
     args.cuda = True
     args.join_query = len(args.relations.split(',')) > 1
     return args

@@ -16,5 +16,7 @@ from . import stax, predict, util  # noqa: E402,F401
 from .batching import batch  # noqa: E402,F401
 from .pool import pool_select_greedy  # noqa: E402,F401
 from .sparse import SparseGPModel, select_inducing  # noqa: E402,F401
+from .matfree import MatrixFreeGPModel, matfree_mse_ensemble  # noqa: E402,F401
 
-__all__ = ["stax", "predict", "batch", "util", "pool_select_greedy", "SparseGPModel", "select_inducing"]
+__all__ = ["stax", "predict", "batch", "util", "pool_select_greedy", "SparseGPModel", "select_inducing",
+           "MatrixFreeGPModel", "matfree_mse_ensemble"]
