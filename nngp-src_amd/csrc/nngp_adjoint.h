@@ -5,7 +5,9 @@
 //   seeds of the marginal likelihood:   alpha_i alpha_j                             and  A^-1_ij
 //   seeds of the leave-one-out loss:    1/2 (alpha_i u_j + u_i alpha_j)             and  C_ij = (A^-1 diag(bbar) A^-1)_ij
 // Everything else -- tiling, Gram staging, forward recursion, reverse sweep, the q = 0 and exact-diagonal rules, the fixed-order
-// reduction -- is one piece of code (adjoint_tile), so both objectives differentiate the same kernel.
+// reduction -- is one piece of code (adjoint_tile), so both objectives differentiate the same kernel.  Its stages are named
+// device functions (tile_q_chain, gram_tile, entry_forward, entry_reverse, ard_sums, reduce_components), of which the rectangular
+// pass of the sparse evidence (rect_tile, sparse_rect.h) is the second user: the layer recursion and its adjoint exist once.
 // With per-feature input relevances (nngp_ard.hip) the same pass also leaves the seeded adjoints at the input of Dense layer 0
 // behind (the ARD flag), from which one contraction with X gives the derivative with respect to every relevance.
 #pragma once
@@ -14,6 +16,7 @@
 #include "trig_tab.h"
 
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 namespace nngp {
@@ -54,7 +57,219 @@ struct AddTerms {
     double* tpart;        // [2 n_terms][nparts]: per term <seed 0, K^(t)> and <seed 1, K^(t)> of the tile
 };
 
+// ---- The pieces of a tile pass: the one copy of every stage that adjoint_tile (below, square, lower tiles) and rect_tile
+// (sparse_rect.h, rectangular) share.  Each is called by the whole 256-thread workgroup of a 64 x 64 tile; thread tid holds the
+// 16 entries (tr + 16 p, tc + 16 q), tc = tid & 15, tr = tid >> 4.  The LDS arrays belong to the tile function and come in by
+// reference, the per-entry state by reference to register arrays; the order of every floating-point operation is fixed here.
 // NLC: room for n_dense <= NLC layers (the per-entry state lives in registers, so its size must be known at compile time).
+
+struct TileRows {
+    const double* p;  // [n, d]
+    int64_t n;        // rows from n on read as zero
+    int64_t r0;       // the tile's first row
+};
+
+// what the reverse sweep of one entry holds once it has passed Dense layer 0: the adjoints of K0_ij, q_i and q_j, of the first
+// seed (a) and of the matrix seed (i)
+struct InputAdjoint {
+    double kb_a, kb_i, q1a, q2a, q1i, q2i;
+};
+
+// The q chain of one of the tile's rows (tid < MT) or columns (tid < 2 MT), in the kernel build's order of operations:
+// qs[l][tid] = q at the input of Dense layer l, rq[l][tid] = 1 / (4 pi q') with q' after it, 0 where q' = 0 (the q = 0 rule)
+template <int NLC>
+__device__ __forceinline__ void tile_q_chain(double q, const ArchDev& arch, double (&qs)[NLC][2 * MT], double (&rq)[NLC][2 * MT]) {
+    const int tid = threadIdx.x, nd = arch.n_dense;
+#pragma unroll
+    for (int l = 0; l < NLC; ++l) {
+        if (l < nd) {
+            qs[l][tid] = q;
+            const double qp = fma(arch.w2[l], q, arch.b2[l]);
+            rq[l][tid] = qp > 0.0 ? 1.0 / (4.0 * kPi * qp) : 0.0;
+            if (l < nd - 1) q = arch.act[l] == NNGP_ACT_ABRELU ? arch.ap[l][2] * qp : 0.5 * qp;
+        }
+    }
+}
+
+// The Gram tile gt[MT][MT + 1] (over sm) of rows `ra` against rows `rb` on the features [kb, ke): 32-feature chunks of both row
+// panels staged in sm, 4 x 4 register accumulation with the features summed in order, gt = acc / (ke - kb).  SIDE: also both
+// sides' sums of squares from the SAME staged values in the SAME order (qa: rows tr + 16 p, qb: columns tc + 16 p), unscaled.
+// Returns 1 / (ke - kb); the caller's barrier comes before gt is read.
+template <bool SIDE>
+__device__ __forceinline__ double gram_tile(const TileRows& ra, const TileRows& rb, int d, int kb, int ke, double* sm,
+                                            double (&qa)[SIDE ? 4 : 1], double (&qb)[SIDE ? 4 : 1]) {
+    const int tid = threadIdx.x, tc = tid & 15, tr = tid >> 4;
+    double (*s1)[MLD] = reinterpret_cast<double (*)[MLD]>(sm);
+    double (*s2)[MLD] = reinterpret_cast<double (*)[MLD]>(sm + MT * MLD);
+    double acc[4][4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[p][q] = 0.0;
+    if constexpr (SIDE) {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) qa[p] = qb[p] = 0.0;
+    }
+    for (int k0 = kb; k0 < ke; k0 += MKC) {
+        const int kc = ke - k0 < MKC ? ke - k0 : MKC;
+        for (int e = tid; e < MT * MKC; e += 256) {
+            const int r = e / MKC, k = e % MKC;
+            const int64_t i = ra.r0 + r, j = rb.r0 + r;
+            s1[r][k] = (k < kc && i < ra.n) ? ra.p[i * d + k0 + k] : 0.0;
+            s2[r][k] = (k < kc && j < rb.n) ? rb.p[j * d + k0 + k] : 0.0;
+        }
+        __syncthreads();
+        for (int k = 0; k < kc; ++k) {
+            double u[4], v[4];
+#pragma unroll
+            for (int p = 0; p < 4; ++p) u[p] = s1[tr + 16 * p][k];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[q] = s2[tc + 16 * q][k];
+#pragma unroll
+            for (int p = 0; p < 4; ++p)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) acc[p][q] = fma(u[p], v[q], acc[p][q]);
+            if constexpr (SIDE) {
+#pragma unroll
+                for (int p = 0; p < 4; ++p) {
+                    qa[p] = fma(u[p], u[p], qa[p]);
+                    qb[p] = fma(v[p], v[p], qb[p]);
+                }
+            }
+        }
+        __syncthreads();
+    }
+    double (*gt)[MT + 1] = reinterpret_cast<double (*)[MT + 1]>(sm);
+    const double inv_d = 1.0 / (double)(ke - kb);
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) gt[tr + 16 * p][tc + 16 * q] = acc[p][q] * inv_d;
+    return inv_d;
+}
+
+__device__ __forceinline__ double gram_tile(const TileRows& ra, const TileRows& rb, int d, int kb, int ke, double* sm) {
+    double none[1];
+    return gram_tile<false>(ra, rb, d, kb, ke, sm, none, none);
+}
+
+// The forward layer recursion of entry (ri, cj) from k = K0_ij.  Per layer: kin = k into Dense l, ck = dK'/dk and cs = (b - a)^2 s
+// of the activation after it.  DIAG && dg: the diagonal form (theta = 0 exactly; q q' - k^2 == 0 holds exactly, so K' has no q
+// dependence); with DIAG = false no such branch exists.  VALUE: value = K_ij, k out of the last Dense layer (else untouched).
+template <int NLC, bool DIAG, bool VALUE>
+__device__ __forceinline__ void entry_forward(double k, bool dg, int ri, int cj, const ArchDev& arch, const double (&qs)[NLC][2 * MT],
+                                              const double* tab, double (&kin)[NLC], double (&ck)[NLC], double (&cs)[NLC],
+                                              double& value) {
+    const int nd = arch.n_dense;
+#pragma unroll
+    for (int l = 0; l < NLC; ++l) {
+        kin[l] = k;
+        ck[l] = 0.0;
+        cs[l] = 0.0;
+        if constexpr (VALUE) {
+            if (l == nd - 1) value = fma(arch.w2[l], k, arch.b2[l]);
+        }
+        if (l < nd - 1) {
+            const double v = arch.w2[l], c = arch.b2[l];
+            const bool ab = arch.act[l] == NNGP_ACT_ABRELU;
+            k = fma(v, k, c);
+            if (DIAG && dg) {  // theta = 0: K' = (a^2 + b^2) / 2 k  (1/2 for ReLU), no q dependence
+                const double kd = ab ? arch.ap[l][2] : 0.5;
+                k *= kd;
+                ck[l] = kd;
+            } else {
+                const double q1 = fma(v, qs[l][ri], c), q2 = fma(v, qs[l][MT + cj], c);
+                const double rr = fma(q1, q2, -k * k);
+                const double s = rr > 0.0 ? fast_sqrt_pos(rr > 0.0 ? rr : 1.0) : 0.0;
+                const double kr = pi_minus_atan2(s, k, tab) * (0.5 / kPi);  // kdot
+                const double kk = fma(kr, k, s * (0.5 / kPi));
+                // ABRelu's form is computed beside ReLU's and one of them chosen: a branch on ab would copy the per-layer arrays
+                const double a0 = arch.ap[l][0], a1 = arch.ap[l][1];
+                const double ka = fma(a0, k, a1 * kk), cka = fma(a1, kr, a0), csa = a1 * s;
+                k = ab ? ka : kk;
+                ck[l] = ab ? cka : kr;
+                cs[l] = ab ? csa : s;
+            }
+        }
+    }
+}
+
+// The reverse sweep of entry (ri, cj).  r comes in as the seeds (kb_a, kb_i; the four q adjoints zero) and leaves as what is left
+// at the input of Dense layer 0; every Dense layer's two components are added into ga / gi on the way.
+template <int NLC>
+__device__ __forceinline__ void entry_reverse(InputAdjoint& r, int ri, int cj, const ArchDev& arch,
+                                              const double (&qs)[NLC][2 * MT], const double (&rq)[NLC][2 * MT],
+                                              const double (&kin)[NLC], const double (&ck)[NLC], const double (&cs)[NLC],
+                                              double (&ga)[2 * NLC], double (&gi)[2 * NLC]) {
+    const int nd = arch.n_dense;
+    double &kb_a = r.kb_a, &kb_i = r.kb_i, &q1a = r.q1a, &q2a = r.q2a, &q1i = r.q1i, &q2i = r.q2i;
+#pragma unroll
+    for (int l = NLC - 1; l >= 0; --l) {
+        if (l < nd) {
+            if (l < nd - 1) {  // the activation after Dense layer l: dK'/dq1 = (b - a)^2 s / (4 pi q1'), q' = h q
+                const double h = arch.act[l] == NNGP_ACT_ABRELU ? arch.ap[l][2] : 0.5;
+                const double t1 = cs[l] * rq[l][ri], t2 = cs[l] * rq[l][MT + cj];
+                q1a = fma(kb_a, t1, h * q1a);
+                q2a = fma(kb_a, t2, h * q2a);
+                kb_a *= ck[l];
+                q1i = fma(kb_i, t1, h * q1i);
+                q2i = fma(kb_i, t2, h * q2i);
+                kb_i *= ck[l];
+            }
+            // Dense layer l: k' = v k + c (likewise q1, q2)
+            const double v = arch.w2[l], x1 = qs[l][ri], x2 = qs[l][MT + cj];
+            ga[2 * l] += fma(kb_a, kin[l], fma(q1a, x1, q2a * x2));
+            ga[2 * l + 1] += kb_a + q1a + q2a;
+            gi[2 * l] += fma(kb_i, kin[l], fma(q1i, x1, q2i * x2));
+            gi[2 * l + 1] += kb_i + q1i + q2i;
+            kb_a *= v;
+            q1a *= v;
+            q2a *= v;
+            kb_i *= v;
+            q1i *= v;
+            q2i *= v;
+        }
+    }
+}
+
+// ARD: the tile's sums of qbar1 over its columns and of qbar2 over its rows.  Every thread adds into slots of its own of
+// rsum [seed][row][tc] / csum [seed][column][tr] in the order of its entries; ard_sums then gives thread tid the sum of the 16
+// slots of array tid >> 6 (0, 1: row sums of seed 0, 1; 2, 3: column sums), row / column tid & 63.
+using ArdSums = double[2][MT][17];
+
+__device__ __forceinline__ void ard_sums_clear(ArdSums& rsum, ArdSums& csum) {
+    for (int e = threadIdx.x; e < 2 * MT * 17; e += 256) (&rsum[0][0][0])[e] = (&csum[0][0][0])[e] = 0.0;
+}
+
+__device__ __forceinline__ double ard_sums(const ArdSums& rsum, const ArdSums& csum) {
+    __syncthreads();
+    const int arr = threadIdx.x >> 6, r = threadIdx.x & (MT - 1);
+    const double* src = arr < 2 ? rsum[arr][r] : csum[arr - 2][r];
+    double t = 0.0;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) t += src[e];
+    return t;
+}
+
+// The tile's 2 n_dense components of either seed, summed over the workgroup in a fixed order into the tile's slot of part
+template <int NLC>
+__device__ __forceinline__ void reduce_components(const double (&ga)[2 * NLC], const double (&gi)[2 * NLC], int nd, double* red,
+                                                  double* part, int64_t nparts) {
+    const int ncomp = 2 * nd;
+#pragma unroll
+    for (int c = 0; c < 2 * NLC; ++c) {
+        if (c < ncomp) {  // uniform over the workgroup
+            const double ra = block_sum(ga[c], red);
+            const double rb = block_sum(gi[c], red);
+            if (threadIdx.x == 0) {
+                part[(int64_t)c * nparts + blockIdx.x] = ra;
+                part[(int64_t)(ncomp + c) * nparts + blockIdx.x] = rb;
+            }
+        }
+    }
+}
+
+// ---- The symmetric pass over the lower tiles ----
 // LOO: the rank-two seed 1/2 (alpha_i u_j + u_i alpha_j) instead of alpha_i alpha_j.
 // ARD: also keep what the reverse sweep holds once it has passed Dense layer 0 -- kbar = S_ij dK_ij/dK0_ij into cmat, and
 // qbar1 = S_ij dK_ij/dq_i, qbar2 = S_ij dK_ij/dq_j summed over the tile's columns / rows into qbar.  Tile (ti, tj) writes its row
@@ -79,26 +294,14 @@ __device__ __forceinline__ void adjoint_tile(const MllArgs& a, const ArchDev& ar
     static_assert(MT * (MT + 1) <= 2 * MT * MLD, "the Gram tile aliases the panels");
     static_assert(!(ARD && ADD), "relevances together with groups are not covered");
     const int tid = threadIdx.x, tc = tid & 15, tr = tid >> 4;
-    if constexpr (ARD) {
-        for (int e = tid; e < 2 * MT * 17; e += 256) (&rsum[0][0][0])[e] = (&csum[0][0][0])[e] = 0.0;
-    }
+    if constexpr (ARD) ard_sums_clear(rsum, csum);
     const int nd = arch.n_dense;
     const int64_t tn = (a.n + MT - 1) / MT;
     int64_t ti, tj;
     lower_tile(xcd_tile(blockIdx.x, tn * (tn + 1) / 2), &ti, &tj);
     const int64_t i0 = ti * MT, j0 = tj * MT;
     for (int e = tid; e < 65 * 4; e += 256) tab[e] = kTrigTab[e >> 2][e & 3];
-    auto q_chain = [&](double q) {  // the q chain of the tile's rows and columns, in the kernel build's order of operations
-#pragma unroll
-        for (int l = 0; l < NLC; ++l) {
-            if (l < nd) {
-                qs[l][tid] = q;
-                const double qp = fma(arch.w2[l], q, arch.b2[l]);
-                rq[l][tid] = qp > 0.0 ? 1.0 / (4.0 * kPi * qp) : 0.0;
-                if (l < nd - 1) q = arch.act[l] == NNGP_ACT_ABRELU ? arch.ap[l][2] * qp : 0.5 * qp;
-            }
-        }
-    };
+    double (*gt)[MT + 1] = reinterpret_cast<double (*)[MT + 1]>(sm);
     double ga[2 * NLC], gi[2 * NLC];
     const int n_terms = ADD ? add.n_terms : 1;
     int t = 0;
@@ -115,57 +318,12 @@ __device__ __forceinline__ void adjoint_tile(const MllArgs& a, const ArchDev& ar
         }
         if (!grp && tid < 2 * MT) {
             const int64_t g = tid < MT ? i0 + tid : j0 + tid - MT;
-            q_chain(g < a.n ? a.q[g] : 0.0);
+            tile_q_chain<NLC>(g < a.n ? a.q[g] : 0.0, arch, qs, rq);
         }
 
         // ---- Gram tile: rows i0 + tr + 16 p, columns j0 + tc + 16 q, features summed in order ----
-        double (*s1)[MLD] = reinterpret_cast<double (*)[MLD]>(sm);
-        double (*s2)[MLD] = reinterpret_cast<double (*)[MLD]>(sm + MT * MLD);
-        double acc[4][4];
         [[maybe_unused]] double qa[ADD ? 4 : 1], qb[ADD ? 4 : 1];
-#pragma unroll
-        for (int p = 0; p < 4; ++p)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) acc[p][q] = 0.0;
-        if constexpr (ADD) {
-#pragma unroll
-            for (int p = 0; p < 4; ++p) qa[p] = qb[p] = 0.0;
-        }
-        for (int k0 = kb; k0 < ke; k0 += MKC) {
-            const int kc = ke - k0 < MKC ? ke - k0 : MKC;
-            for (int e = tid; e < MT * MKC; e += 256) {
-                const int r = e / MKC, k = e % MKC;
-                const int64_t i = i0 + r, j = j0 + r;
-                s1[r][k] = (k < kc && i < a.n) ? a.x[i * a.d + k0 + k] : 0.0;
-                s2[r][k] = (k < kc && j < a.n) ? a.x[j * a.d + k0 + k] : 0.0;
-            }
-            __syncthreads();
-            for (int k = 0; k < kc; ++k) {
-                double u[4], v[4];
-#pragma unroll
-                for (int p = 0; p < 4; ++p) u[p] = s1[tr + 16 * p][k];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) v[q] = s2[tc + 16 * q][k];
-#pragma unroll
-                for (int p = 0; p < 4; ++p)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) acc[p][q] = fma(u[p], v[q], acc[p][q]);
-                if constexpr (ADD) {
-#pragma unroll
-                    for (int p = 0; p < 4; ++p) {
-                        qa[p] = fma(u[p], u[p], qa[p]);
-                        qb[p] = fma(v[p], v[p], qb[p]);
-                    }
-                }
-            }
-            __syncthreads();
-        }
-        double (*gt)[MT + 1] = reinterpret_cast<double (*)[MT + 1]>(sm);
-        const double inv_d = 1.0 / (double)(ke - kb);
-#pragma unroll
-        for (int p = 0; p < 4; ++p)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) gt[tr + 16 * p][tc + 16 * q] = acc[p][q] * inv_d;
+        [[maybe_unused]] const double inv_d = gram_tile<ADD>(TileRows{a.x, a.n, i0}, TileRows{a.x, a.n, j0}, a.d, kb, ke, sm, qa, qb);
         if constexpr (ADD) {
             if (grp) {  // every row / column of the tile has 16 threads with the same sums: one of them writes
 #pragma unroll
@@ -178,7 +336,7 @@ __device__ __forceinline__ void adjoint_tile(const MllArgs& a, const ArchDev& ar
         __syncthreads();
         if constexpr (ADD) {
             if (grp) {
-                if (tid < 2 * MT) q_chain(qg[tid]);
+                if (tid < 2 * MT) tile_q_chain<NLC>(qg[tid], arch, qs, rq);
                 __syncthreads();
             }
         }
@@ -197,104 +355,38 @@ __device__ __forceinline__ void adjoint_tile(const MllArgs& a, const ArchDev& ar
             // a group's term takes the diagonal form wherever both slices give k == q == q' bit for bit (the diagonal does)
             const bool dg = grp ? (qs[0][ri] == gt[ri][cj] && qs[0][MT + cj] == gt[ri][cj]) : i == j;
             const double w = i == j ? 1.0 : 2.0;  // the lower triangle stands for the whole square
-            double kb_a;
-            if constexpr (LOO) kb_a = w * (0.5 * (a.alpha[i] * a.u[j] + a.u[i] * a.alpha[j]));
-            else kb_a = w * (a.alpha[i] * a.alpha[j]);
-            double kb_i = w * a.ainv[i * a.ld + j];
-            double k = dg ? qs[0][ri] : gt[ri][cj];  // exact diagonal: q q' - k^2 == 0 holds exactly
-            double kin[NLC], ck[NLC], cs[NLC];  // per layer: k into Dense l; dK'/dk and (b - a)^2 s of the activation after it
-#pragma unroll
-            for (int l = 0; l < NLC; ++l) {
-                kin[l] = k;
-                ck[l] = 0.0;
-                cs[l] = 0.0;
-                if constexpr (ADD) {
-                    if (l == nd - 1) {  // K^(t)_ij, out of the last Dense layer
-                        const double val = fma(arch.w2[l], k, arch.b2[l]);
-                        ha = fma(kb_a, val, ha);
-                        hi = fma(kb_i, val, hi);
-                    }
-                }
-                if (l < nd - 1) {
-                    const double v = arch.w2[l], c = arch.b2[l];
-                    const bool ab = arch.act[l] == NNGP_ACT_ABRELU;
-                    k = fma(v, k, c);
-                    if (dg) {  // theta = 0: K' = (a^2 + b^2) / 2 k  (1/2 for ReLU), no q dependence
-                        const double kd = ab ? arch.ap[l][2] : 0.5;
-                        k *= kd;
-                        ck[l] = kd;
-                    } else {
-                        const double q1 = fma(v, qs[l][ri], c), q2 = fma(v, qs[l][MT + cj], c);
-                        const double rr = fma(q1, q2, -k * k);
-                        const double s = rr > 0.0 ? fast_sqrt_pos(rr > 0.0 ? rr : 1.0) : 0.0;
-                        const double kr = pi_minus_atan2(s, k, tab) * (0.5 / kPi);  // kdot
-                        const double kk = fma(kr, k, s * (0.5 / kPi));
-                        if (ab) {
-                            k = fma(arch.ap[l][0], k, arch.ap[l][1] * kk);
-                            ck[l] = fma(arch.ap[l][1], kr, arch.ap[l][0]);
-                            cs[l] = arch.ap[l][1] * s;
-                        } else {
-                            k = kk;
-                            ck[l] = kr;
-                            cs[l] = s;
-                        }
-                    }
-                }
-            }
+            InputAdjoint r{0.0, w * a.ainv[i * a.ld + j], 0.0, 0.0, 0.0, 0.0};  // the seeds
+            if constexpr (LOO) r.kb_a = w * (0.5 * (a.alpha[i] * a.u[j] + a.u[i] * a.alpha[j]));
+            else r.kb_a = w * (a.alpha[i] * a.alpha[j]);
+            const double k = dg ? qs[0][ri] : gt[ri][cj];  // exact diagonal: q q' - k^2 == 0 holds exactly
+            double kin[NLC], ck[NLC], cs[NLC];
+            [[maybe_unused]] double val = 0.0;  // ADD: K^(t)_ij
+            entry_forward<NLC, true, ADD>(k, dg, ri, cj, arch, qs, tab, kin, ck, cs, val);
             if constexpr (ADD) {
+                ha = fma(r.kb_a, val, ha);
+                hi = fma(r.kb_i, val, hi);
                 if (wt == 0.0) continue;  // the term is not in K: its own d/dw_t only
-                kb_a *= wt;
-                kb_i *= wt;
+                r.kb_a *= wt;
+                r.kb_i *= wt;
             }
-            double q1a = 0.0, q2a = 0.0, q1i = 0.0, q2i = 0.0;
-#pragma unroll
-            for (int l = NLC - 1; l >= 0; --l) {
-                if (l < nd) {
-                    if (l < nd - 1) {  // the activation after Dense layer l: dK'/dq1 = (b - a)^2 s / (4 pi q1'), q' = h q
-                        const double h = arch.act[l] == NNGP_ACT_ABRELU ? arch.ap[l][2] : 0.5;
-                        const double t1 = cs[l] * rq[l][ri], t2 = cs[l] * rq[l][MT + cj];
-                        q1a = fma(kb_a, t1, h * q1a);
-                        q2a = fma(kb_a, t2, h * q2a);
-                        kb_a *= ck[l];
-                        q1i = fma(kb_i, t1, h * q1i);
-                        q2i = fma(kb_i, t2, h * q2i);
-                        kb_i *= ck[l];
-                    }
-                    // Dense layer l: k' = v k + c (likewise q1, q2)
-                    const double v = arch.w2[l], x1 = qs[l][ri], x2 = qs[l][MT + cj];
-                    ga[2 * l] += fma(kb_a, kin[l], fma(q1a, x1, q2a * x2));
-                    ga[2 * l + 1] += kb_a + q1a + q2a;
-                    gi[2 * l] += fma(kb_i, kin[l], fma(q1i, x1, q2i * x2));
-                    gi[2 * l + 1] += kb_i + q1i + q2i;
-                    kb_a *= v;
-                    q1a *= v;
-                    q2a *= v;
-                    kb_i *= v;
-                    q1i *= v;
-                    q2i *= v;
-                }
-            }
+            entry_reverse<NLC>(r, ri, cj, arch, qs, rq, kin, ck, cs, ga, gi);
             if constexpr (ARD) {
                 if (dg) {
-                    rsum[0][ri][tc] += kb_a;
-                    rsum[1][ri][tc] += kb_i;
+                    rsum[0][ri][tc] += r.kb_a;
+                    rsum[1][ri][tc] += r.kb_i;
                 } else {
-                    a.cmat[i * a.ldc + j] = kb_a;
-                    a.cmat[j * a.ldc + i] = kb_i;
-                    rsum[0][ri][tc] += q1a;
-                    rsum[1][ri][tc] += q1i;
-                    csum[0][cj][tr] += q2a;
-                    csum[1][cj][tr] += q2i;
+                    a.cmat[i * a.ldc + j] = r.kb_a;
+                    a.cmat[j * a.ldc + i] = r.kb_i;
+                    rsum[0][ri][tc] += r.q1a;
+                    rsum[1][ri][tc] += r.q1i;
+                    csum[0][cj][tr] += r.q2a;
+                    csum[1][cj][tr] += r.q2i;
                 }
             }
         }
         if constexpr (ARD) {
-            __syncthreads();
+            const double t = ard_sums(rsum, csum);
             const int arr = tid >> 6, r = tid & (MT - 1);  // 0, 1: row sums of seed 0, 1; 2, 3: column sums
-            const double* src = arr < 2 ? rsum[arr][r] : csum[arr - 2][r];
-            double t = 0.0;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) t += src[e];
             red[tid] = t;
             __syncthreads();
             if (ti == tj) {
@@ -313,18 +405,7 @@ __device__ __forceinline__ void adjoint_tile(const MllArgs& a, const ArchDev& ar
             }
         }
     } while (ADD && ++t < n_terms);
-    const int ncomp = 2 * nd;
-#pragma unroll
-    for (int c = 0; c < 2 * NLC; ++c) {
-        if (c < ncomp) {  // uniform over the workgroup
-            const double ra = block_sum(ga[c], red);
-            const double rb = block_sum(gi[c], red);
-            if (tid == 0) {
-                a.part[(int64_t)c * a.nparts + blockIdx.x] = ra;
-                a.part[(int64_t)(ncomp + c) * a.nparts + blockIdx.x] = rb;
-            }
-        }
-    }
+    reduce_components<NLC>(ga, gi, nd, red, a.part, a.nparts);
 }
 
 // out[e] = sum_i q_i^(e), the diagonal's q at the input of Dense layer e (one workgroup, fixed order): tr dK/dtheta follows from
@@ -422,6 +503,23 @@ struct nngp_mll {
 };
 
 namespace nngp {
+// The one ladder from n_dense to the NLC a tile pass is instantiated for.  launch(std::integral_constant<int, NLC>{}, grid)
+// launches the pass's kernel on `grid`, one workgroup per tile; who prefixes the error.
+template <class Launch>
+int launch_by_nlc(const ArchDev& arch, int64_t nparts, const char* who, Launch launch) {
+    NNGP_REQUIRE(nparts < 2147483647LL, "%s: gradient grid too large", who);
+    const dim3 grid((unsigned)nparts);
+    if (arch.n_dense <= 2) launch(std::integral_constant<int, 2>{}, grid);
+    else if (arch.n_dense <= 4) launch(std::integral_constant<int, 4>{}, grid);
+    else if (arch.n_dense <= 8) launch(std::integral_constant<int, 8>{}, grid);
+    else launch(std::integral_constant<int, NNGP_MAX_DENSE>{}, grid);
+    NNGP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+// The two symmetric passes that the sparse evidence runs over K_uu as well, both handle-free: the plain pass (nngp_mll.hip,
+// k_nngp_mll_partial) and the pass with ARD set (nngp_ard.hip, k_nngp_ard_partial; a.cmat / a.qbar filled in by the caller)
+int launch_mll_partial(const MllArgs& a, const ArchDev& arch, hipStream_t s);
+int launch_ard_partial(const MllArgs& a, const ArchDev& arch, bool loo, hipStream_t s);
 // nngp_mll.hip: the architecture checked for the float64 gradient paths (rc -2 naming `who`), and A = K + r I (get: NNGP_GET_NNGP,
 // or NNGP_GET_NTK for Theta + r I) in w.a with the identity on the padding; red[0] = tr K, red[1] = r
 // x, q: the inputs and their row norms (the handle's own, or the scaled copy of ArdBuffers)
@@ -437,8 +535,8 @@ int mll_evaluate_core(nngp_mll* h, const nngp_arch_act* arch_in, double diag_reg
                       double* grad_w = nullptr);
 int loo_evaluate_core(nngp_mll* h, const nngp_arch_act* arch_in, int get, double diag_reg, int absolute, int objective, double* value,
                       double* grad, const double* rel, double* grad_s, const char* who, hipStream_t s);
-// nngp_ard.hip.  ard_begin: checks rel, uploads it, fills ard.xs and ard.q.  launch_ard_partial: the adjoint pass with ARD set
-// (a.cmat / a.qbar filled in from the handle).  ard_contract: the contraction and its finish into ard.out, queued for the host
+// nngp_ard.hip.  ard_begin: checks rel, uploads it, fills ard.xs and ard.q.  launch_ard_partial(h, ...): the adjoint pass with ARD set
+// (a.cmat / a.qbar filled in from the handle, then the handle-free launcher above).  ard_contract: the contraction and its finish into ard.out, queued for the host
 // copy ard.host.  ard_finish_host (after the stream is synchronised): grad_s and the terms from ard.host; s1, s2 multiply
 // lambda tr dK / N in the two halves (alpha^T alpha, tr A^-1; or alpha^T u, tr C), loo picks -(h1 + h2) over -h1/2 + h2/2.
 int ard_begin(nngp_mll* h, const double* rel, const char* who, hipStream_t s);

@@ -32,18 +32,15 @@ __global__ __launch_bounds__(256) void k_nngp_ard_partial(MllArgs a, ArchDev arc
     adjoint_tile<NLC, LOO, true>(a, arch);
 }
 
-template <bool LOO>
-int launch_partial(const MllArgs& a, const ArchDev& arch, hipStream_t s) {
-    const dim3 grid((unsigned)a.nparts), block(256);
-    if (arch.n_dense <= 2) hipLaunchKernelGGL((k_nngp_ard_partial<2, LOO>), grid, block, 0, s, a, arch);
-    else if (arch.n_dense <= 4) hipLaunchKernelGGL((k_nngp_ard_partial<4, LOO>), grid, block, 0, s, a, arch);
-    else if (arch.n_dense <= 8) hipLaunchKernelGGL((k_nngp_ard_partial<8, LOO>), grid, block, 0, s, a, arch);
-    else hipLaunchKernelGGL((k_nngp_ard_partial<NNGP_MAX_DENSE, LOO>), grid, block, 0, s, a, arch);
-    NNGP_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
 }  // namespace
+
+int launch_ard_partial(const MllArgs& a, const ArchDev& arch, bool loo, hipStream_t s) {
+    return launch_by_nlc(arch, a.nparts, "mll", [&](auto nlc, dim3 grid) {
+        constexpr int NLC = decltype(nlc)::value;
+        if (loo) hipLaunchKernelGGL((k_nngp_ard_partial<NLC, true>), grid, dim3(256), 0, s, a, arch);
+        else hipLaunchKernelGGL((k_nngp_ard_partial<NLC, false>), grid, dim3(256), 0, s, a, arch);
+    });
+}
 
 int ard_begin(nngp_mll* h, const double* rel, const char* who, hipStream_t s) {
     ArdBuffers& a = h->ard;
@@ -60,12 +57,11 @@ int ard_begin(nngp_mll* h, const double* rel, const char* who, hipStream_t s) {
 }
 
 int launch_ard_partial(nngp_mll* h, MllArgs a, const ArchDev& arch, bool loo, hipStream_t s) {
-    NNGP_REQUIRE(a.nparts < 2147483647LL, "mll: gradient grid too large");
     a.cmat = h->w.zt;
     a.ldc = h->w.np;
     a.qbar = h->ard.qbar;
     a.np = h->w.np;
-    return loo ? launch_partial<true>(a, arch, s) : launch_partial<false>(a, arch, s);
+    return launch_ard_partial(a, arch, loo, s);
 }
 
 int ard_contract(nngp_mll* h, hipStream_t s) {

@@ -97,14 +97,9 @@ __global__ __launch_bounds__(256) void k_loo_finish(const double* c, int64_t ld,
 }
 
 int launch_loo_partial(const MllArgs& a, const ArchDev& arch, hipStream_t s) {
-    NNGP_REQUIRE(a.nparts < 2147483647LL, "mll_loo: gradient grid too large");
-    const dim3 grid((unsigned)a.nparts), block(256);
-    if (arch.n_dense <= 2) hipLaunchKernelGGL(k_nngp_loo_partial<2>, grid, block, 0, s, a, arch);
-    else if (arch.n_dense <= 4) hipLaunchKernelGGL(k_nngp_loo_partial<4>, grid, block, 0, s, a, arch);
-    else if (arch.n_dense <= 8) hipLaunchKernelGGL(k_nngp_loo_partial<8>, grid, block, 0, s, a, arch);
-    else hipLaunchKernelGGL(k_nngp_loo_partial<NNGP_MAX_DENSE>, grid, block, 0, s, a, arch);
-    NNGP_HIP_CHECK(hipGetLastError());
-    return 0;
+    return launch_by_nlc(arch, a.nparts, "mll_loo", [&](auto nlc, dim3 grid) {
+        hipLaunchKernelGGL(k_nngp_loo_partial<decltype(nlc)::value>, grid, dim3(256), 0, s, a, arch);
+    });
 }
 
 // c (lower triangle, by row panels that end at the diagonal) <- zs ainv^T.  Timing key 15 = 1: the whole square in one product.

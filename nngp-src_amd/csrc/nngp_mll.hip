@@ -71,18 +71,13 @@ __global__ __launch_bounds__(256) void k_mll_finish(const double* l, int64_t ldl
     }
 }
 
-int launch_mll_partial(const MllArgs& a, const ArchDev& arch, hipStream_t s) {
-    NNGP_REQUIRE(a.nparts < 2147483647LL, "mll: gradient grid too large");
-    const dim3 grid((unsigned)a.nparts), block(256);
-    if (arch.n_dense <= 2) hipLaunchKernelGGL(k_nngp_mll_partial<2>, grid, block, 0, s, a, arch);
-    else if (arch.n_dense <= 4) hipLaunchKernelGGL(k_nngp_mll_partial<4>, grid, block, 0, s, a, arch);
-    else if (arch.n_dense <= 8) hipLaunchKernelGGL(k_nngp_mll_partial<8>, grid, block, 0, s, a, arch);
-    else hipLaunchKernelGGL(k_nngp_mll_partial<NNGP_MAX_DENSE>, grid, block, 0, s, a, arch);
-    NNGP_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
 }  // namespace
+
+int launch_mll_partial(const MllArgs& a, const ArchDev& arch, hipStream_t s) {
+    return launch_by_nlc(arch, a.nparts, "mll", [&](auto nlc, dim3 grid) {
+        hipLaunchKernelGGL(k_nngp_mll_partial<decltype(nlc)::value>, grid, dim3(256), 0, s, a, arch);
+    });
+}
 
 int mll_make_arch(const nngp_arch_act* arch_in, double diag_reg, const char* who, ArchDev* out) {
     ArchDev& arch = *out;

@@ -105,16 +105,11 @@ int add_begin(nngp_mll* h, const double* weights, const char* who, const GroupsD
 int launch_add_partial(nngp_mll* h, const MllArgs& a, const ArchDev& arch, hipStream_t s) {
     const AddBuffers& b = h->add;
     const int G = b.n_terms - 1;
-    NNGP_REQUIRE(a.nparts < 2147483647LL, "mll: gradient grid too large");
     NNGP_REQUIRE(2 * (int64_t)b.n_terms * a.nparts <= h->w.np * h->w.np, "mll: the term partials do not fit the L^-T storage");
     const AddTerms add{b.n_terms, b.range, b.range + G, b.weight, h->w.zt};
-    const dim3 grid((unsigned)a.nparts), block(256);
-    if (arch.n_dense <= 2) hipLaunchKernelGGL(k_mll_add_partial<2>, grid, block, 0, s, a, arch, add);
-    else if (arch.n_dense <= 4) hipLaunchKernelGGL(k_mll_add_partial<4>, grid, block, 0, s, a, arch, add);
-    else if (arch.n_dense <= 8) hipLaunchKernelGGL(k_mll_add_partial<8>, grid, block, 0, s, a, arch, add);
-    else hipLaunchKernelGGL(k_mll_add_partial<NNGP_MAX_DENSE>, grid, block, 0, s, a, arch, add);
-    NNGP_HIP_CHECK(hipGetLastError());
-    return 0;
+    return launch_by_nlc(arch, a.nparts, "mll", [&](auto nlc, dim3 grid) {
+        hipLaunchKernelGGL(k_mll_add_partial<decltype(nlc)::value>, grid, dim3(256), 0, s, a, arch, add);
+    });
 }
 
 int launch_add_finish(nngp_mll* h, const ArchDev& arch, int64_t nparts, hipStream_t s) {

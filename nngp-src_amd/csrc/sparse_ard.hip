@@ -15,8 +15,8 @@
 //                               with the RAW U, then sum_{i in I} x_ik (Z_ik + e1_i x_ik), rows in order, and sum_{i in I} x_ik^2
 //   k_sparse_ard_finish         the row blocks summed in ascending order and added to the accumulators, chunk after chunk; likewise
 //                               e2_j += the chunk's row tiles in order
-// and once per call: the symmetric half over K_uu (adjoint_tile<NLC, false, true> seeded with gamma and E, then k_ard_contract of
-// ard_contract.h with the raw U), and k_sparse_ard_cols, sum_j e2_j u_jk^2.  No float atomics, no device-side counter, no workgroup
+// and once per call: the symmetric half over K_uu (launch_ard_partial of nngp_ard.hip, k_nngp_ard_partial<NLC, false>, seeded with
+// gamma and E, then k_ard_contract of ard_contract.h with the raw U), and k_sparse_ard_cols, sum_j e2_j u_jk^2.  No float atomics, no device-side counter, no workgroup
 // waits for another: launch boundaries are the only synchronisation, every slot has one writer and every sum a fixed order.
 #include "ard_contract.h"
 #include "sparse_rect.h"
@@ -36,11 +36,6 @@ __global__ __launch_bounds__(256) void k_sparse_ard_scale(const double* x, const
 template <int NLC>
 __global__ __launch_bounds__(256) void k_sparse_rect_ard_partial(RectArgs a, ArchDev arch) {
     rect_tile<NLC, true>(a, arch);
-}
-
-template <int NLC>
-__global__ __launch_bounds__(256) void k_sparse_uu_ard_partial(MllArgs a, ArchDev arch) {
-    adjoint_tile<NLC, false, true>(a, arch);
 }
 
 // grid (row blocks of the chunk, feature chunks, 2 halves).  kb0 / kb1: [c, ld] kbar of the rank-one / the dense seed; x: [c, d] and
@@ -142,24 +137,9 @@ __global__ __launch_bounds__(256) void k_sparse_ard_cols(const double* e2, int64
 }
 
 int launch_rect_ard(const RectArgs& a, const ArchDev& arch, hipStream_t s) {
-    NNGP_REQUIRE(a.nparts < 2147483647LL, "sparse_ard: gradient grid too large");
-    const dim3 grid((unsigned)a.nparts), block(256);
-    if (arch.n_dense <= 2) hipLaunchKernelGGL(k_sparse_rect_ard_partial<2>, grid, block, 0, s, a, arch);
-    else if (arch.n_dense <= 4) hipLaunchKernelGGL(k_sparse_rect_ard_partial<4>, grid, block, 0, s, a, arch);
-    else if (arch.n_dense <= 8) hipLaunchKernelGGL(k_sparse_rect_ard_partial<8>, grid, block, 0, s, a, arch);
-    else hipLaunchKernelGGL(k_sparse_rect_ard_partial<NNGP_MAX_DENSE>, grid, block, 0, s, a, arch);
-    NNGP_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-int launch_uu_ard(const MllArgs& a, const ArchDev& arch, hipStream_t s) {
-    const dim3 grid((unsigned)a.nparts), block(256);
-    if (arch.n_dense <= 2) hipLaunchKernelGGL(k_sparse_uu_ard_partial<2>, grid, block, 0, s, a, arch);
-    else if (arch.n_dense <= 4) hipLaunchKernelGGL(k_sparse_uu_ard_partial<4>, grid, block, 0, s, a, arch);
-    else if (arch.n_dense <= 8) hipLaunchKernelGGL(k_sparse_uu_ard_partial<8>, grid, block, 0, s, a, arch);
-    else hipLaunchKernelGGL(k_sparse_uu_ard_partial<NNGP_MAX_DENSE>, grid, block, 0, s, a, arch);
-    NNGP_HIP_CHECK(hipGetLastError());
-    return 0;
+    return launch_by_nlc(arch, a.nparts, "sparse_ard", [&](auto nlc, dim3 grid) {
+        hipLaunchKernelGGL(k_sparse_rect_ard_partial<decltype(nlc)::value>, grid, dim3(256), 0, s, a, arch);
+    });
 }
 
 // the rectangular pass with ARD set over one block, its contraction and the finish into acc [3 d] / e2 [2][mpc]
@@ -211,7 +191,7 @@ int sparse_ard_uu(nngp_sparse* h, const double* seed, const double* gamma, doubl
     const int64_t m = h->m, mp = h->mp, tn = (m + MT - 1) / MT;
     const int d = h->d;
     MllArgs ma{h->u, h->uq, m, d, seed, mp, gamma, nullptr, h->ev_part, gp_lower_tiles(m), cmat, mp, h->ard_qbar, mp};
-    NNGP_TRY(launch_uu_ard(ma, h->arch, s));
+    NNGP_TRY(launch_ard_partial(ma, h->arch, false, s));
     const dim3 grid((unsigned)tn, (unsigned)((d + AKC - 1) / AKC), 2);
     hipLaunchKernelGGL(k_ard_contract, grid, dim3(256), 0, s, cmat, mp, h->ard_u, m, d, h->ard_qbar, mp, tn, h->ard_part);
     hipLaunchKernelGGL(k_ard_finish, dim3((unsigned)((3 * d + 255) / 256)), dim3(256), 0, s, h->ard_part, tn, d, h->ard_acc + 5 * d);

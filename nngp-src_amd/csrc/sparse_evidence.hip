@@ -5,17 +5,18 @@
 // The gradient hands the rows again and contracts dK / dtheta with its seeds entry by entry, never forming it:
 //
 //   once per call   K~_uu^-1, M = L_u^-T B^-1 L_u^-1 and gamma on the float64 core of gp_f64.hip (triangular solves of the identity
-//                   and products on the float64 MFMA GEMM); then the symmetric adjoint pass of nngp_adjoint.h over K_uu
-//                   (adjoint_tile<NLC, false, false>: alpha := gamma, the matrix seed := E with the jitter's share on its diagonal)
+//                   and products on the float64 MFMA GEMM); then the exact evidence's symmetric adjoint pass over K_uu
+//                   (launch_mll_partial of nngp_mll.hip, k_nngp_mll_partial: alpha := gamma, the matrix seed := E with the
+//                   jitter's share on its diagonal)
 //   per chunk       the cross build K_cu (no solve), beta_c = (y_c - K_cu gamma) / sigma2, D_c = K_cu M' on the MFMA GEMM, and
 //   k_sparse_rect_partial   (sparse_rect.h) the adjoint of the layer recursion over the rectangular block K(X_c, U).  One workgroup
-//                   per 64 x 64 tile of (rows of X_c) x (rows of U); it mirrors adjoint_tile -- the q chains of the tile's rows
-//                   and columns in the kernel build's order of operations, the Gram tile from LDS-staged feature chunks, per entry
-//                   the forward recursion (ReLU and ABRelu, the q = 0 rule, pi_minus_atan2 on kTrigTab) and the reverse sweep --
-//                   but every entry of the tile counts once, there is no exact-diagonal rule (a training row that is also an
-//                   inducing row takes the general formula, as in the cross build), and the seeds are the rank-one beta_i gamma_j
-//                   (the "quad" half) and the dense D[i, j] (the "trace" half).  Each tile writes its 2 n_dense partials per half
-//                   to a slot of its own;
+//                   per 64 x 64 tile of (rows of X_c) x (rows of U); it runs the pieces of nngp_adjoint.h that adjoint_tile
+//                   runs -- the q chains of the tile's rows and columns in the kernel build's order of operations, the Gram
+//                   tile from LDS-staged feature chunks, per entry the forward recursion (ReLU and ABRelu, the q = 0 rule,
+//                   pi_minus_atan2 on kTrigTab) and the reverse sweep -- but every entry of the tile counts once, there is no
+//                   exact-diagonal rule (a training row that is also an inducing row takes the general formula, as in the
+//                   cross build), and the seeds are the rank-one beta_i gamma_j (the "quad" half) and the dense D[i, j] (the
+//                   "trace" half).  Each tile writes its 2 n_dense partials per half to a slot of its own;
 //   k_ev_reduce     one workgroup sums the slots in ascending order and adds the chunk's sums to the accumulators.
 // No float atomics, no device-side counter, no workgroup waits for another: a launch boundary is the only synchronisation, so
 // nothing here can hang and two runs give the same bits.
@@ -32,12 +33,6 @@ __global__ __launch_bounds__(256) void k_sparse_rect_partial(RectArgs a, ArchDev
     rect_tile<NLC>(a, arch);
 }
 
-// the symmetric pass over K_uu: the exact evidence's own device code, seeded with gamma and E
-template <int NLC>
-__global__ __launch_bounds__(256) void k_sparse_uu_partial(MllArgs a, ArchDev arch) {
-    adjoint_tile<NLC, false, false>(a, arch);
-}
-
 // acc[c] += sum over the nparts slots of component c, in ascending order (one workgroup)
 __global__ __launch_bounds__(256) void k_ev_reduce(const double* part, int64_t nparts, int ncomp4, double* acc) {
     __shared__ double red[256];
@@ -45,11 +40,6 @@ __global__ __launch_bounds__(256) void k_ev_reduce(const double* part, int64_t n
         const double r = finish_part(part, nparts, c, red);
         if (threadIdx.x == 0) acc[c] += r;
     }
-}
-
-__global__ __launch_bounds__(256) void k_ev_eye(double* a, int64_t ld, int64_t n) {
-    const int64_t i = blockIdx.y, j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (j < n) a[i * ld + j] = i == j ? 1.0 : 0.0;
 }
 
 // dst (full square) <- G, of which only the 128 x 128 tiles on or below the diagonal are kept
@@ -137,24 +127,9 @@ __global__ __launch_bounds__(256) void k_ev_qsums(const double* q, int64_t c, Ar
 }
 
 int launch_rect(const RectArgs& a, const ArchDev& arch, hipStream_t s) {
-    NNGP_REQUIRE(a.nparts < 2147483647LL, "sparse_evidence: gradient grid too large");
-    const dim3 grid((unsigned)a.nparts), block(256);
-    if (arch.n_dense <= 2) hipLaunchKernelGGL(k_sparse_rect_partial<2>, grid, block, 0, s, a, arch);
-    else if (arch.n_dense <= 4) hipLaunchKernelGGL(k_sparse_rect_partial<4>, grid, block, 0, s, a, arch);
-    else if (arch.n_dense <= 8) hipLaunchKernelGGL(k_sparse_rect_partial<8>, grid, block, 0, s, a, arch);
-    else hipLaunchKernelGGL(k_sparse_rect_partial<NNGP_MAX_DENSE>, grid, block, 0, s, a, arch);
-    NNGP_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-int launch_uu(const MllArgs& a, const ArchDev& arch, hipStream_t s) {
-    const dim3 grid((unsigned)a.nparts), block(256);
-    if (arch.n_dense <= 2) hipLaunchKernelGGL(k_sparse_uu_partial<2>, grid, block, 0, s, a, arch);
-    else if (arch.n_dense <= 4) hipLaunchKernelGGL(k_sparse_uu_partial<4>, grid, block, 0, s, a, arch);
-    else if (arch.n_dense <= 8) hipLaunchKernelGGL(k_sparse_uu_partial<8>, grid, block, 0, s, a, arch);
-    else hipLaunchKernelGGL(k_sparse_uu_partial<NNGP_MAX_DENSE>, grid, block, 0, s, a, arch);
-    NNGP_HIP_CHECK(hipGetLastError());
-    return 0;
+    return launch_by_nlc(arch, a.nparts, "sparse_evidence", [&](auto nlc, dim3 grid) {
+        hipLaunchKernelGGL(k_sparse_rect_partial<decltype(nlc)::value>, grid, dim3(256), 0, s, a, arch);
+    });
 }
 
 int reduce_into(const double* part, int64_t nparts, int ncomp4, double* acc, hipStream_t s) {
@@ -296,12 +271,12 @@ int nngp::sparse_evidence_grad_core(nngp_sparse* h, const double* x, const doubl
     NNGP_HIP_CHECK(hipMemsetAsync(h->scal + kSpSums, 0, sizeof(double) * (kSpScal - kSpSums), s));
     NNGP_TRY(value_sums(h, s));
     // tr B^-1 = |L_B^-T|_F^2
-    hipLaunchKernelGGL(k_ev_eye, sq, dim3(256), 0, s, T, mp, mp);
+    hipLaunchKernelGGL(k_eye, sq, dim3(256), 0, s, T, mp, mp);
     NNGP_HIP_CHECK(hipGetLastError());
     NNGP_TRY(trsm_fwd_f64(T, mp, mp, h->lb, mp, h->dinv_b, mp, scratch, true, s));
     hipLaunchKernelGGL(k_rowdot, dim3((unsigned)m), dim3(256), 0, s, T, mp, m, nullptr, nullptr, 0.0, rowsq, 0.0);
     // T = L_u^-T
-    hipLaunchKernelGGL(k_ev_eye, sq, dim3(256), 0, s, T, mp, mp);
+    hipLaunchKernelGGL(k_eye, sq, dim3(256), 0, s, T, mp, mp);
     NNGP_HIP_CHECK(hipGetLastError());
     NNGP_TRY(trsm_fwd_f64(T, mp, mp, h->lu, mp, h->dinv_u, mp, scratch, true, s));
     if (vfe) {  // M = L_u^-T G L_u^-1
@@ -334,7 +309,7 @@ int nngp::sparse_evidence_grad_core(nngp_sparse* h, const double* x, const doubl
             NNGP_TRY(sparse_ard_uu(h, M, gamma, T, s));
         } else {
             MllArgs ma{h->u, h->uq, m, h->d, M, mp, gamma, nullptr, h->ev_part, tiles};
-            NNGP_TRY(launch_uu(ma, h->arch, s));
+            NNGP_TRY(launch_mll_partial(ma, h->arch, s));  // the exact evidence's own pass, seeded with gamma and E
         }
         NNGP_TRY(reduce_into(h->ev_part, tiles, 2 * ncomp, h->scal + kSpAccUu, s));
     }

@@ -1,7 +1,9 @@
 // The rectangular adjoint pass of the sparse evidence (sparse_evidence.hip) as device code shared with the relevance gradient
-// (sparse_ard.hip): one workgroup per 64 x 64 tile of (rows of X_c) x (rows of U), mirroring adjoint_tile of nngp_adjoint.h but
-// with every entry counted once and no exact-diagonal rule.  With ARD set the pass also leaves behind what its reverse sweep
-// holds once it has passed Dense layer 0 -- the seeded adjoints of K0_ij, q_i and q_j -- for the contraction with the raw rows.
+// (sparse_ard.hip): one workgroup per 64 x 64 tile of (rows of X_c) x (rows of U).  Every stage -- q chain, Gram tile, forward
+// recursion, reverse sweep, the reductions -- is the piece of nngp_adjoint.h that adjoint_tile runs; what is this tile's own is
+// the tile index, the two row sources, the tails, the seeds, that every entry counts once with no exact-diagonal rule, and where
+// the ARD left-overs go.  With ARD set the pass also leaves behind what its reverse sweep holds once it has passed Dense layer
+// 0 -- the seeded adjoints of K0_ij, q_i and q_j -- for the contraction with the raw rows.
 #pragma once
 #include "nngp_adjoint.h"
 
@@ -33,8 +35,7 @@ struct RectArgs {
 };
 
 // ARD: also keep kbar = S_ij dK_ij/dK0_ij (both seeds) and the sums of qbar1 = S_ij dK_ij/dq_i over the tile's columns and of
-// qbar2 = S_ij dK_ij/dq_j over its rows, laid out as adjoint_tile's rsum / csum: every thread sums into slots of its own in the
-// order of its entries, and every global slot has one writer.  The ARD = false instantiation is the pass as it was.
+// qbar2 = S_ij dK_ij/dq_j over its rows (ard_sums); every global slot has one writer.
 // Static LDS with ARD at NLC = 16: 33 792 (panels) + 32 768 (qs, rq) + 2 080 + 2 048 + 34 816 (rsum, csum) = 105 504 bytes, as
 // adjoint_tile<16, ., true>; within gfx950's 160 KiB per workgroup, above the 64 KiB of older parts.
 template <int NLC, bool ARD = false>
@@ -49,67 +50,21 @@ __device__ __forceinline__ void rect_tile(const RectArgs& a, const ArchDev& arch
                   "static LDS beyond a gfx950 workgroup's 160 KiB");
     static_assert(MT * (MT + 1) <= 2 * MT * MLD, "the Gram tile aliases the panels");
     const int tid = threadIdx.x, tc = tid & 15, tr = tid >> 4;
-    if constexpr (ARD) {
-        for (int e = tid; e < 2 * MT * 17; e += 256) (&rsum[0][0][0])[e] = (&csum[0][0][0])[e] = 0.0;
-    }
-    const int nd = arch.n_dense;
+    if constexpr (ARD) ard_sums_clear(rsum, csum);
     const int64_t t = xcd_tile(blockIdx.x, a.nparts);
     const int64_t i0 = (t / a.tu) * MT, j0 = (t % a.tu) * MT;
     for (int e = tid; e < 65 * 4; e += 256) tab[e] = kTrigTab[e >> 2][e & 3];
-    if (tid < 2 * MT) {  // the q chain of the tile's rows and columns, in the kernel build's order of operations
+    if (tid < 2 * MT) {
         double q;
         if (tid < MT) q = i0 + tid < a.c ? a.xq[i0 + tid] : 0.0;
         else q = j0 + tid - MT < a.m ? a.uq[j0 + tid - MT] : 0.0;
-#pragma unroll
-        for (int l = 0; l < NLC; ++l) {
-            if (l < nd) {
-                qs[l][tid] = q;
-                const double qp = fma(arch.w2[l], q, arch.b2[l]);
-                rq[l][tid] = qp > 0.0 ? 1.0 / (4.0 * kPi * qp) : 0.0;
-                if (l < nd - 1) q = arch.act[l] == NNGP_ACT_ABRELU ? arch.ap[l][2] * qp : 0.5 * qp;
-            }
-        }
+        tile_q_chain<NLC>(q, arch, qs, rq);
     }
-
-    // ---- Gram tile: rows i0 + tr + 16 p of X_c, columns j0 + tc + 16 q of U, features summed in order ----
-    double (*s1)[MLD] = reinterpret_cast<double (*)[MLD]>(sm);
-    double (*s2)[MLD] = reinterpret_cast<double (*)[MLD]>(sm + MT * MLD);
-    double acc[4][4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc[p][q] = 0.0;
-    for (int k0 = 0; k0 < a.d; k0 += MKC) {
-        const int kc = a.d - k0 < MKC ? a.d - k0 : MKC;
-        for (int e = tid; e < MT * MKC; e += 256) {
-            const int r = e / MKC, k = e % MKC;
-            const int64_t i = i0 + r, j = j0 + r;
-            s1[r][k] = (k < kc && i < a.c) ? a.x[i * a.d + k0 + k] : 0.0;
-            s2[r][k] = (k < kc && j < a.m) ? a.u[j * a.d + k0 + k] : 0.0;
-        }
-        __syncthreads();
-        for (int k = 0; k < kc; ++k) {
-            double uu[4], vv[4];
-#pragma unroll
-            for (int p = 0; p < 4; ++p) uu[p] = s1[tr + 16 * p][k];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) vv[q] = s2[tc + 16 * q][k];
-#pragma unroll
-            for (int p = 0; p < 4; ++p)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[p][q] = fma(uu[p], vv[q], acc[p][q]);
-        }
-        __syncthreads();
-    }
+    // rows i0 + tr + 16 p of X_c against columns j0 + tc + 16 q of U
+    gram_tile(TileRows{a.x, a.c, i0}, TileRows{a.u, a.m, j0}, a.d, 0, a.d, sm);
     double (*gt)[MT + 1] = reinterpret_cast<double (*)[MT + 1]>(sm);
-    const double inv_d = 1.0 / (double)a.d;
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) gt[tr + 16 * p][tc + 16 * q] = acc[p][q] * inv_d;
     __syncthreads();
 
-    // ---- per entry: forward recursion, then the adjoint sweep from both seeds ----
     double ga[2 * NLC], gi[2 * NLC];
 #pragma unroll
     for (int c = 0; c < 2 * NLC; ++c) ga[c] = gi[c] = 0.0;
@@ -118,94 +73,27 @@ __device__ __forceinline__ void rect_tile(const RectArgs& a, const ArchDev& arch
         const int ri = tr + 16 * (e >> 2), cj = tc + 16 * (e & 3);
         const int64_t i = i0 + ri, j = j0 + cj;
         if (i >= a.c || j >= a.m) continue;  // the tile's tails
-        double kb_a = a.beta[i] * a.gamma[j];
-        double kb_i = a.seed[i * a.ld + j];
-        double k = gt[ri][cj];
-        double kin[NLC], ck[NLC], cs[NLC];  // per layer: k into Dense l; dK'/dk and (b - a)^2 s of the activation after it
-#pragma unroll
-        for (int l = 0; l < NLC; ++l) {
-            kin[l] = k;
-            ck[l] = 0.0;
-            cs[l] = 0.0;
-            if (l < nd - 1) {
-                const double v = arch.w2[l], c = arch.b2[l];
-                const bool ab = arch.act[l] == NNGP_ACT_ABRELU;
-                k = fma(v, k, c);
-                const double q1 = fma(v, qs[l][ri], c), q2 = fma(v, qs[l][MT + cj], c);
-                const double rr = fma(q1, q2, -k * k);
-                const double s = rr > 0.0 ? fast_sqrt_pos(rr > 0.0 ? rr : 1.0) : 0.0;
-                const double kr = pi_minus_atan2(s, k, tab) * (0.5 / kPi);  // kdot
-                const double kk = fma(kr, k, s * (0.5 / kPi));
-                if (ab) {
-                    k = fma(arch.ap[l][0], k, arch.ap[l][1] * kk);
-                    ck[l] = fma(arch.ap[l][1], kr, arch.ap[l][0]);
-                    cs[l] = arch.ap[l][1] * s;
-                } else {
-                    k = kk;
-                    ck[l] = kr;
-                    cs[l] = s;
-                }
-            }
-        }
-        double q1a = 0.0, q2a = 0.0, q1i = 0.0, q2i = 0.0;
-#pragma unroll
-        for (int l = NLC - 1; l >= 0; --l) {
-            if (l < nd) {
-                if (l < nd - 1) {  // the activation after Dense layer l: dK'/dq1 = (b - a)^2 s / (4 pi q1'), q' = h q
-                    const double h = arch.act[l] == NNGP_ACT_ABRELU ? arch.ap[l][2] : 0.5;
-                    const double t1 = cs[l] * rq[l][ri], t2 = cs[l] * rq[l][MT + cj];
-                    q1a = fma(kb_a, t1, h * q1a);
-                    q2a = fma(kb_a, t2, h * q2a);
-                    kb_a *= ck[l];
-                    q1i = fma(kb_i, t1, h * q1i);
-                    q2i = fma(kb_i, t2, h * q2i);
-                    kb_i *= ck[l];
-                }
-                // Dense layer l: k' = v k + c (likewise q1, q2)
-                const double v = arch.w2[l], x1 = qs[l][ri], x2 = qs[l][MT + cj];
-                ga[2 * l] += fma(kb_a, kin[l], fma(q1a, x1, q2a * x2));
-                ga[2 * l + 1] += kb_a + q1a + q2a;
-                gi[2 * l] += fma(kb_i, kin[l], fma(q1i, x1, q2i * x2));
-                gi[2 * l + 1] += kb_i + q1i + q2i;
-                kb_a *= v;
-                q1a *= v;
-                q2a *= v;
-                kb_i *= v;
-                q1i *= v;
-                q2i *= v;
-            }
-        }
+        // a training row that is also an inducing row takes the general formula, as in the cross build
+        InputAdjoint r{a.beta[i] * a.gamma[j], a.seed[i * a.ld + j], 0.0, 0.0, 0.0, 0.0};  // the seeds
+        double kin[NLC], ck[NLC], cs[NLC], none;
+        entry_forward<NLC, false, false>(gt[ri][cj], false, ri, cj, arch, qs, tab, kin, ck, cs, none);
+        entry_reverse<NLC>(r, ri, cj, arch, qs, rq, kin, ck, cs, ga, gi);
         if constexpr (ARD) {
-            a.kb_a[i * a.ld + j] = kb_a;
-            a.kb_i[i * a.ld + j] = kb_i;
-            rsum[0][ri][tc] += q1a;
-            rsum[1][ri][tc] += q1i;
-            csum[0][cj][tr] += q2a;
-            csum[1][cj][tr] += q2i;
+            a.kb_a[i * a.ld + j] = r.kb_a;
+            a.kb_i[i * a.ld + j] = r.kb_i;
+            rsum[0][ri][tc] += r.q1a;
+            rsum[1][ri][tc] += r.q1i;
+            csum[0][cj][tr] += r.q2a;
+            csum[1][cj][tr] += r.q2i;
         }
     }
     if constexpr (ARD) {
-        __syncthreads();
+        const double sum = ard_sums(rsum, csum);
         const int arr = tid >> 6, r = tid & (MT - 1);  // 0, 1: row sums of seed 0, 1; 2, 3: column sums
-        const double* src = arr < 2 ? rsum[arr][r] : csum[arr - 2][r];
-        double sum = 0.0;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) sum += src[e];
         if (arr < 2) a.qrow[((int64_t)arr * a.tu + t % a.tu) * a.cp + i0 + r] = sum;
         else a.qcol[((int64_t)(arr - 2) * a.tr + t / a.tu) * a.mpc + j0 + r] = sum;
     }
-    const int ncomp = 2 * nd;
-#pragma unroll
-    for (int c = 0; c < 2 * NLC; ++c) {
-        if (c < ncomp) {  // uniform over the workgroup
-            const double ra = block_sum(ga[c], red);
-            const double rb = block_sum(gi[c], red);
-            if (tid == 0) {
-                a.part[(int64_t)c * a.nparts + blockIdx.x] = ra;
-                a.part[(int64_t)(ncomp + c) * a.nparts + blockIdx.x] = rb;
-            }
-        }
-    }
+    reduce_components<NLC>(ga, gi, arch.n_dense, red, a.part, a.nparts);
 }
 
 }  // namespace nngp
