@@ -149,6 +149,12 @@ int launch_row_sqnorm(const double* x, int64_t n, int d, double* q, hipStream_t 
 int launch_diag_from_q(const double* q, int64_t n, const ArchDev& arch, double* dn, double* dt, hipStream_t s);
 int launch_kernel_build(const BuildArgs& a, const ArchDev& arch, hipStream_t s);  // arch.groups: the summed kernel
 int launch_kernel_build_plain(const BuildArgs& a, const ArchDev& arch, hipStream_t s);  // the whole-input term alone
+// The 64 x 64 tiling of a build, for the plain and the additive launch: the requirements (d > 0, the full row range in symmetric
+// mode, the grid limit), the tile counts and the workgroups of a one-tile-per-workgroup kernel (lower tiles when symmetric;
+// *nblocks = 0: nothing to build).  *vec_ok: 16-byte stores are legal -- every row start is 16-byte aligned for every output in use
+// (columns start at multiples of 4).  rows_at_4: the plain build also wants row_begin % 4 == 0; the additive build does not
+// (its mirror's columns are rows of a symmetric build, which starts at row 0).
+int plan_build_tiles(const BuildArgs& a, bool rows_at_4, int64_t* tiles_r, int64_t* tiles_c, int64_t* nblocks, int* vec_ok);
 // K's diagonal of rows x (q = |x|^2 / d): launch_diag_from_q, or the grouped diagonal when arch.groups is set
 int launch_kernel_diag(const double* x, const double* q, int64_t n, int d, const ArchDev& arch, double* dn, double* dt,
                        hipStream_t s);

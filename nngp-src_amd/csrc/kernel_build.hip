@@ -11,10 +11,7 @@
 //
 // Everything is float64: the GP solve behind this kernel has cond ~ 1e7, and a float32 Gram
 // perturbs posterior means by ~2.5e-4, over the 1e-4 parity gate.
-#include "common.h"
-#include "trig_tab.h"
-#include "f64_math.h"
-#include "act_map.h"
+#include "kernel_tile.h"
 #include <math.h>
 #include <mutex>
 #include <type_traits>
@@ -24,12 +21,9 @@ namespace nngp {
 
 namespace {
 
-constexpr int KT = 64;       // output tile edge
 constexpr int KC = 16;       // k-chunk staged per iteration
-constexpr int LDP = KT + 2;  // LDS row stride in doubles (keeps 16-byte alignment of every row)
 constexpr int LDM = KT + 16; // staging stride of the MFMA variant: 2*LDM = 32 (mod 64) dwords, so the four k-rows a
                              // v_mfma_f64_16x16x4 fragment read touches fall on disjoint bank halves (conflict free)
-typedef double f64x4 __attribute__((ext_vector_type(4)));
 constexpr int kCompNI = 16, kCompDeg = 10;                       // intervals of [0, pi] and polynomial degree of the composite map
 constexpr int kCompSize = kCompNI * (kCompDeg + 1) + 1;          // + the amplitude A
 
@@ -116,28 +110,10 @@ __device__ __forceinline__ void layer_map(double k, double q1, double q2, const 
 __device__ __forceinline__ void layer_map_act(double k, double q1, double q2, const ArchDev& arch, bool exact_diag,
                                               double& out_k, double& out_t);
 
-template <typename T>
-__device__ __forceinline__ void store4(T* base, int64_t ld, int64_t i, int64_t j, int64_t i_end, int64_t j_end,
-                                       const double v[4], bool vec_ok) {
-    if (base == nullptr || i >= i_end) return;
-    T* p = base + i * ld + j;
-    if (vec_ok && j + 3 < j_end) {
-        if constexpr (sizeof(T) == 8) {
-            reinterpret_cast<double2*>(p)[0] = make_double2(v[0], v[1]);
-            reinterpret_cast<double2*>(p)[1] = make_double2(v[2], v[3]);
-        } else {
-            reinterpret_cast<float4*>(p)[0] = make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
-        }
-    } else {
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-            if (j + c < j_end) p[c] = (T)v[c];
-    }
-}
-
 // MFMA = true: the Gram entries x.x' are accumulated on the float64 matrix cores (v_mfma_f64_16x16x4_f64, 2x2 tiles of
 // 16x16 per wave, 4 waves = the 64x64 tile) and handed to the epilogue's 4x4-per-thread layout through LDS;
-// MFMA = false: the same sums on the float64 VALU (the default; the MFMA form is selected by nngp_debug_set(3, 3)).
+// MFMA = false: the same sums on the float64 VALU.  The round-1 kernel, kept for A/B timing and as a second implementation the
+// tests hold the product form (k_build_mfma below) against: nngp_debug_set(3, 4) selects MFMA = false, (3, 3) MFMA = true.
 // Arch = ArchDev: a network with other activations than ReLU (layer_map_act).
 template <bool MFMA, typename Arch = ArchRelu>
 __global__ __launch_bounds__(256) void k_build(BuildArgs a, Arch arch, int64_t tiles_c, int vec_ok) {
@@ -151,11 +127,7 @@ __global__ __launch_bounds__(256) void k_build(BuildArgs a, Arch arch, int64_t t
 
     int64_t bi, bj;
     if (a.sym) {
-        const int64_t p = blockIdx.x;
-        bi = (int64_t)((sqrt(8.0 * (double)p + 1.0) - 1.0) * 0.5);
-        while (bi * (bi + 1) / 2 > p) --bi;
-        while ((bi + 1) * (bi + 2) / 2 <= p) ++bi;
-        bj = p - bi * (bi + 1) / 2;
+        lower_tile(blockIdx.x, &bi, &bj);
     } else {
         bi = blockIdx.x / tiles_c;
         bj = blockIdx.x % tiles_c;
@@ -280,53 +252,8 @@ __global__ __launch_bounds__(256) void k_build(BuildArgs a, Arch arch, int64_t t
     }
     const bool vec = vec_ok != 0;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int64_t gi = i0 + ty + 16 * r, gj = j0 + tx * 4;
-        store4(a.nngp64, a.ld64, gi, gj, i_end, j_end, kn[r], vec);
-        store4(a.ntk64, a.ld64, gi, gj, i_end, j_end, kt[r], vec);
-        if (a.nngp32 != nullptr || a.ntk32 != nullptr) {  // float32 copies (factorisation input): regulariser on the diagonal
-            double vn[4], vt[4];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const bool diag = a.sym && gi == gj + c;
-                vn[c] = kn[r][c] + (diag ? a.diag_add_nngp32 : 0.0);
-                vt[c] = kt[r][c] + (diag ? a.diag_add_ntk32 : 0.0);
-            }
-            store4(a.nngp32, a.ld32, gi, gj, i_end, j_end, vn, vec);
-            store4(a.ntk32, a.ld32, gi, gj, i_end, j_end, vt, vec);
-        }
-    }
-
-    // ---- mirror image of an off-diagonal tile (symmetric build): transpose through LDS ----
-    if (a.sym && bi != bj) {
-        for (int which = 0; which < 2; ++which) {
-            if (which == 0 && a.nngp64 == nullptr && a.nngp32 == nullptr) continue;
-            if (which == 1 && a.ntk64 == nullptr && a.ntk32 == nullptr) continue;
-            __syncthreads();
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int c = 0; c < 4; ++c)
-                    smem[(tx * 4 + c) * LDP + ty + 16 * r] = which == 0 ? kn[r][c] : kt[r][c];
-            __syncthreads();
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                double v[4];
-                const double2 v01 = *reinterpret_cast<const double2*>(&smem[(ty + 16 * r) * LDP + tx * 4]);
-                const double2 v23 = *reinterpret_cast<const double2*>(&smem[(ty + 16 * r) * LDP + tx * 4 + 2]);
-                v[0] = v01.x; v[1] = v01.y; v[2] = v23.x; v[3] = v23.y;
-                // element (j0 + ty + 16 r, i0 + tx*4 + c); rows bounded by n2 (= n1), columns by row_end
-                const int64_t mi = j0 + ty + 16 * r, mj = i0 + tx * 4;
-                if (which == 0) {
-                    store4(a.nngp64, a.ld64, mi, mj, j_end, i_end, v, vec);
-                    if (!a.lower32) store4(a.nngp32, a.ld32, mi, mj, j_end, i_end, v, vec);
-                } else {
-                    store4(a.ntk64, a.ld64, mi, mj, j_end, i_end, v, vec);
-                    if (!a.lower32) store4(a.ntk32, a.ld32, mi, mj, j_end, i_end, v, vec);
-                }
-            }
-        }
-    }
+    for (int r = 0; r < 4; ++r) tile_store_4x4<true>(a, i0, j0, r, kn, kt, vec);
+    if (a.sym && bi != bj) tile_mirror_4x4<true>(a, i0, j0, smem, kn, kt, vec);
 }
 
 // ---- the other activations: act_diag / act_cross in act_map.h ----
@@ -359,15 +286,7 @@ __global__ __launch_bounds__(256) void k_diag_from_q_act(const double* __restric
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     double k = q[i], t = 0.0;
-    for (int l = 0; l < arch.n_dense; ++l) {
-        k = fma(arch.w2[l], k, arch.b2[l]);
-        t = fma(arch.w2[l], t, k);
-        if (l < arch.n_dense - 1) {
-            double kd;
-            act_diag(arch.act[l], arch.ap[l], k, &kTrigTab[0][0], k, kd);
-            t *= kd;
-        }
-    }
+    diag_chain_act(arch, &kTrigTab[0][0], k, t);
     if (dn) dn[i] = k;
     if (dt) dt[i] = t;
 }
@@ -402,15 +321,12 @@ constexpr int TLD = 34;       // row stride of the per-wave 16 x 32 output buffe
 template <int MKC, bool PREFETCH, int MINWG, bool LDSOUT, bool COMP, bool GEN = false>
 __global__ __launch_bounds__(256, MINWG) void k_build_mfma(BuildArgs a, std::conditional_t<GEN, ArchDev, ArchRelu> arch, int64_t tiles_r, int64_t tiles_c,
                                                            int64_t sup_r, int64_t sup_c, int vec_ok, int ablate) {
-    constexpr int MLD = MKC + 2;  // LDS row stride (doubles): rows 16-byte aligned, quarter-waves on distinct banks
-    constexpr int NLD = MKC * 64 / 256;  // doubles per thread and operand per chunk
+    constexpr int MLD = panel_ld(MKC);
     __shared__ __attribute__((aligned(16))) double smem[2 * KT * MLD];  // As | Bs in the k-loop, 4 output buffers afterwards
     __shared__ __attribute__((aligned(16))) double tab[65 * 4];
     __shared__ double ctab[COMP ? kCompSize : 1];
-    __shared__ double qs[GEN ? (NNGP_MAX_DENSE - 1) * 2 * KT : 1];  // [layer][64 rows | 64 columns], before the activation
+    __shared__ double qs[GEN ? (NNGP_MAX_DENSE - 1) * 2 * KT : 1];  // stage_layer_q
     static_assert(4 * 16 * TLD <= 2 * KT * MLD, "the output buffers alias the panel buffers");
-    double* As = smem;             // [KT][MLD]
-    double* Bs = smem + KT * MLD;  // [KT][MLD]
     const int tid = threadIdx.x;
 
     // workgroup -> tile: XCD = blockIdx % 8; each XCD walks whole super-tiles of 8 x 8 tiles
@@ -420,10 +336,7 @@ __global__ __launch_bounds__(256, MINWG) void k_build_mfma(BuildArgs a, std::con
     int64_t sbi, sbj;
     if (a.sym) {
         if (sid >= sup_r * (sup_r + 1) / 2) return;
-        sbi = (int64_t)((sqrt(8.0 * (double)sid + 1.0) - 1.0) * 0.5);
-        while (sbi * (sbi + 1) / 2 > sid) --sbi;
-        while ((sbi + 1) * (sbi + 2) / 2 <= sid) ++sbi;
-        sbj = sid - sbi * (sbi + 1) / 2;
+        lower_tile(sid, &sbi, &sbj);
     } else {
         if (sid >= sup_r * sup_c) return;
         sbi = sid / sup_c;
@@ -439,69 +352,14 @@ __global__ __launch_bounds__(256, MINWG) void k_build_mfma(BuildArgs a, std::con
     if constexpr (GEN) {  // read after the k-loop's first barrier
         if (tid < 2 * KT) {
             const int64_t g = tid < KT ? i0 + tid : j0 + tid - KT;
-            double q = tid < KT ? (g < i_end ? a.q1[g] : 0.0) : (g < j_end ? a.q2[g] : 0.0);
-            for (int l = 0; l < arch.n_dense - 1; ++l) {
-                double unused;
-                q = fma(arch.w2[l], q, arch.b2[l]);
-                qs[l * 2 * KT + tid] = q;
-                act_diag(arch.act[l], arch.ap[l], q, &kTrigTab[0][0], q, unused);
-            }
+            stage_layer_q(tid < KT ? (g < i_end ? a.q1[g] : 0.0) : (g < j_end ? a.q2[g] : 0.0), arch, qs);
         }
     }
 
     const int lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1, l16 = lane & 15, lg = lane >> 4;
     f64x4 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.0;
-
-    double ra[NLD], rb[NLD];
-    auto load_chunk = [&](int k0) {  // 64 rows x MKC k per operand, lanes along k
-#pragma unroll
-        for (int e = 0; e < NLD; ++e) {
-            const int idx = tid + 256 * e;
-            const int kk = idx & (MKC - 1), row = idx / MKC;
-            const int kg = k0 + kk;
-            const int64_t gi = i0 + row, gj = j0 + row;
-            ra[e] = (kg < a.d && gi < i_end) ? a.x1[gi * a.d + kg] : 0.0;
-            rb[e] = (kg < a.d && gj < j_end) ? a.x2[gj * a.d + kg] : 0.0;
-        }
-    };
-    if (PREFETCH) load_chunk(0);
-    for (int k0 = 0; k0 < ((ablate & 2) ? MKC : a.d); k0 += MKC) {
-        if (!PREFETCH) load_chunk(k0);
-#pragma unroll
-        for (int e = 0; e < NLD; ++e) {
-            const int idx = tid + 256 * e;
-            const int kk = idx & (MKC - 1), row = idx / MKC;
-            As[row * MLD + kk] = ra[e];
-            Bs[row * MLD + kk] = rb[e];
-        }
-        __syncthreads();
-        if (PREFETCH && k0 + MKC < a.d) load_chunk(k0 + MKC);
-#pragma unroll
-        for (int ks = 0; ks < MKC / 8; ++ks) {
-            double2 fa[2], fb[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                fa[i] = *reinterpret_cast<const double2*>(&As[(wm * 32 + i * 16 + l16) * MLD + ks * 8 + 2 * lg]);
-                fb[i] = *reinterpret_cast<const double2*>(&Bs[(wn * 32 + i * 16 + l16) * MLD + ks * 8 + 2 * lg]);
-            }
-            // lane group g supplies k = 8 ks + 2 g (first MFMA) and 8 ks + 2 g + 1 (second): the sum over k does not care
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[i].x, fb[j].x, acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[i].y, fb[j].y, acc[i][j], 0, 0, 0);
-                }
-        }
-        __syncthreads();
-    }
+    gram_mfma_64<MKC, PREFETCH>(PanelRows{a.x1, i0, i_end}, PanelRows{a.x2, j0, j_end}, a.d, (ablate & 2) ? MKC : a.d, smem, acc);
 
     // ---- layer recursion in the accumulator layout: entry (row = 16 i + lg + 4 r, col = 16 j + l16) of the wave's block ----
     const double inv_d = 1.0 / (double)a.d;
@@ -509,7 +367,6 @@ __global__ __launch_bounds__(256, MINWG) void k_build_mfma(BuildArgs a, std::con
     const bool diag_tile = a.sym && bi == bj && wm == wn;  // entries (i, i) exist only in these blocks
     const bool mirror = a.sym && bi != bj;
     const bool vec = vec_ok != 0;
-    const bool want_t = a.ntk64 != nullptr || a.ntk32 != nullptr;
     double* tbuf = smem + wave * (16 * TLD);  // this wave's output buffer (As / Bs are dead: the k-loop ended with a barrier)
     double q2in[2];
 #pragma unroll
@@ -566,49 +423,9 @@ __global__ __launch_bounds__(256, MINWG) void k_build_mfma(BuildArgs a, std::con
                     kv[j][r] = k;
                 }
             } else if constexpr (GEN) {
-                for (int l = 0; l < arch.n_dense; ++l) {
-                    const double w2 = arch.w2[l], b2 = arch.b2[l];
-                    const bool hidden = l < arch.n_dense - 1;
-                    const int code = hidden ? arch.act[l] : NNGP_ACT_RELU;
-                    const double* ap = arch.ap[hidden ? l : 0];
-                    const double q2l = hidden ? qs[l * 2 * KT + KT + wn * 32 + j * 16 + l16] : 0.0;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        double k = fma(w2, kv[j][r], b2);
-                        double t = fma(w2, tv[j][r], k);
-                        if (hidden) {
-                            double kd;
-                            if (dg[r]) act_diag(code, ap, k, tab, k, kd);  // theta = 0 exactly, as in k_diag_from_q_act
-                            else act_cross(code, ap, k, qs[l * 2 * KT + wm * 32 + i * 16 + lg + 4 * r], q2l, tab, k, kd);
-                            t *= kd;
-                        }
-                        kv[j][r] = k;
-                        tv[j][r] = t;
-                    }
-                }
-            } else
-            for (int l = 0; l < arch.n_dense; ++l) {
-                const double w2 = arch.w2[l], b2 = arch.b2[l];
-                const bool relu = l < arch.n_dense - 1 && !(ablate & 4);
-                q2v = fma(w2, q2v, b2);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    q1v[r] = fma(w2, q1v[r], b2);
-                    double k = fma(w2, kv[j][r], b2);
-                    double t = fma(w2, tv[j][r], k);
-                    if (relu) {
-                        const double rr = dg[r] ? 0.0 : fma(q1v[r], q2v, -k * k);
-                        const double s = rr > 0.0 ? fast_sqrt_pos(rr > 0.0 ? rr : 1.0) : 0.0;
-                        double kd = pi_minus_atan2(s, k, tab) * (0.5 / kPi);
-                        kd = dg[r] ? 0.5 : kd;  // theta = 0 on the diagonal, exactly
-                        k = fma(kd, k, s * (0.5 / kPi));
-                        t *= kd;
-                    }
-                    kv[j][r] = k;
-                    tv[j][r] = t;
-                    q1v[r] *= 0.5;
-                }
-                q2v *= 0.5;
+                gen_block_map<true, 0, 4>(arch, tab, qs, wm * 32 + i * 16 + lg, KT + wn * 32 + j * 16 + l16, kv[j], tv[j], dg);
+            } else {
+                relu_block_map<true, 0, 4>(arch, !(ablate & 4), tab, kv[j], tv[j], q1v, q2v, dg);
             }
         }
         if ((ablate & 1) && kv[0][0] != 12345.678 && tv[1][3] != 12345.678) continue;
@@ -700,7 +517,6 @@ __global__ __launch_bounds__(256, MINWG) void k_build_mfma(BuildArgs a, std::con
             }
         }
     }
-    (void)want_t;
 }
 
 }  // namespace
@@ -842,30 +658,49 @@ int launch_kernel_build(const BuildArgs& a, const ArchDev& arch, hipStream_t s) 
     return launch_kernel_build_plain(a, arch, s);
 }
 
+int plan_build_tiles(const BuildArgs& a, bool rows_at_4, int64_t* tiles_r, int64_t* tiles_c, int64_t* nblocks, int* vec_ok) {
+    *tiles_r = *tiles_c = *nblocks = 0;
+    *vec_ok = 0;
+    const int64_t rows = a.row_end - a.row_begin;
+    if (rows <= 0 || a.n2 <= 0) return 0;
+    NNGP_REQUIRE(a.d > 0, "kernel_build: d must be positive");
+    *tiles_r = (rows + KT - 1) / KT;
+    *tiles_c = (a.n2 + KT - 1) / KT;
+    if (a.sym) {
+        NNGP_REQUIRE(a.row_begin == 0 && a.row_end == a.n1 && a.n1 == a.n2,
+                     "kernel_build: symmetric mode needs the full row range");
+        *nblocks = *tiles_r * (*tiles_r + 1) / 2;
+    } else {
+        *nblocks = *tiles_r * *tiles_c;
+    }
+    NNGP_REQUIRE(*nblocks < (int64_t)2147483647, "kernel_build: grid too large (%lld tiles)", (long long)*nblocks);
+    auto aligned = [](const void* p, int64_t ld, int esz) {
+        return p == nullptr || ((((uintptr_t)p) & 15) == 0 && ((ld * esz) & 15) == 0);
+    };
+    *vec_ok = aligned(a.nngp64, a.ld64, 8) && aligned(a.ntk64, a.ld64, 8) && aligned(a.nngp32, a.ld32, 4) &&
+              aligned(a.ntk32, a.ld32, 4) && (!rows_at_4 || a.row_begin % 4 == 0);
+    return 0;
+}
+
+// The grid of k_build_mfma: 64 tile slots per super-tile of 8 x 8 tiles, super-tiles dealt round-robin to 8 XCDs
+static int mfma_grid(int64_t tiles_r, int64_t tiles_c, int sym, int64_t* sup_r, int64_t* sup_c, int64_t* grid) {
+    *sup_r = (tiles_r + 7) / 8;
+    *sup_c = (tiles_c + 7) / 8;
+    const int64_t nsup = sym ? *sup_r * (*sup_r + 1) / 2 : *sup_r * *sup_c;
+    *grid = ((nsup + 7) / 8) * 8 * 64;
+    NNGP_REQUIRE(*grid < (int64_t)2147483647, "kernel_build: grid too large (%lld workgroups)", (long long)*grid);
+    return 0;
+}
+
 int launch_kernel_build_plain(const BuildArgs& a_in, const ArchDev& arch_in, hipStream_t s) {
     const ArchRelu arch = relu_arch(arch_in);  // the ReLU instantiations' argument (arch_in.general == 0)
     BuildArgs a = a_in;
     // NNGP outputs only, no biases, >= 2 ReLU layers: the composite map (debug key 5 = 63: the per-layer recursion)
     a.comp = (a.ntk64 == nullptr && a.ntk32 == nullptr && !a.no_comp && NNGP_KNOB(5) != 63) ? comp_table(arch_in) : nullptr;
-    const int64_t rows = a.row_end - a.row_begin;
-    if (rows <= 0 || a.n2 <= 0) return 0;
-    NNGP_REQUIRE(a.d > 0, "kernel_build: d must be positive");
-    const int64_t tiles_r = (rows + KT - 1) / KT, tiles_c = (a.n2 + KT - 1) / KT;
-    int64_t nblocks;
-    if (a.sym) {
-        NNGP_REQUIRE(a.row_begin == 0 && a.row_end == a.n1 && a.n1 == a.n2,
-                     "kernel_build: symmetric mode needs the full row range");
-        nblocks = tiles_r * (tiles_r + 1) / 2;
-    } else {
-        nblocks = tiles_r * tiles_c;
-    }
-    NNGP_REQUIRE(nblocks < (int64_t)2147483647, "kernel_build: grid too large (%lld tiles)", (long long)nblocks);
-    // 16-byte stores are legal when every row start is 16-byte aligned for every output in use
-    auto aligned = [](const void* p, int64_t ld, int esz) {
-        return p == nullptr || ((((uintptr_t)p) & 15) == 0 && ((ld * esz) & 15) == 0);
-    };
-    int vec_ok = aligned(a.nngp64, a.ld64, 8) && aligned(a.ntk64, a.ld64, 8) && aligned(a.nngp32, a.ld32, 4) &&
-                 aligned(a.ntk32, a.ld32, 4) && (a.row_begin % 4 == 0);
+    int64_t tiles_r, tiles_c, nblocks, sup_r, sup_c, grid;
+    int vec_ok;
+    NNGP_TRY(plan_build_tiles(a, true, &tiles_r, &tiles_c, &nblocks, &vec_ok));
+    if (nblocks == 0) return 0;
     // Round 1 (scripts/k1_study.py, N=32768, d=128, n_relu=3): the all-VALU kernel k_build<false> took 10.7 ms -- 3.3 ms Gram
     // (41 TF/s float64 FMA), 1.7 ms per ReLU layer (libm sqrt + atan2), 3.0 ms stores; its MFMA variant was slower because it
     // re-tiled the accumulators through LDS and staged the panels k-major (8-way bank conflicts on the stores).  k_build_mfma
@@ -875,10 +710,7 @@ int launch_kernel_build_plain(const BuildArgs& a_in, const ArchDev& arch_in, hip
         if (NNGP_KNOB(3) == 4)
             hipLaunchKernelGGL((k_build<false, ArchDev>), dim3((unsigned)nblocks), dim3(256), 0, s, a, arch_in, tiles_c, vec_ok);
         else {
-            const int64_t sup_r = (tiles_r + 7) / 8, sup_c = (tiles_c + 7) / 8;
-            const int64_t nsup = a.sym ? sup_r * (sup_r + 1) / 2 : sup_r * sup_c;
-            const int64_t grid = ((nsup + 7) / 8) * 8 * 64;
-            NNGP_REQUIRE(grid < (int64_t)2147483647, "kernel_build: grid too large (%lld workgroups)", (long long)grid);
+            NNGP_TRY(mfma_grid(tiles_r, tiles_c, a.sym, &sup_r, &sup_c, &grid));
             hipLaunchKernelGGL((k_build_mfma<16, true, 3, false, false, true>), dim3((unsigned)grid), dim3(256), 0, s, a, arch_in,
                                tiles_r, tiles_c, sup_r, sup_c, vec_ok, 0);
         }
@@ -888,14 +720,11 @@ int launch_kernel_build_plain(const BuildArgs& a_in, const ArchDev& arch_in, hip
         else
             hipLaunchKernelGGL(k_build<false>, dim3((unsigned)nblocks), dim3(256), 0, s, a, arch, tiles_c, vec_ok);
     } else {
-        const int64_t sup_r = (tiles_r + 7) / 8, sup_c = (tiles_c + 7) / 8;
-        const int64_t nsup = a.sym ? sup_r * (sup_r + 1) / 2 : sup_r * sup_c;
-        const int64_t grid = ((nsup + 7) / 8) * 8 * 64;  // 64 tile slots per super-tile, super-tiles dealt round-robin to 8 XCDs
         // (Measured and dropped: a persistent grid of 3 workgroups per compute unit walking the slots -- the 133 k one-tile
         // workgroups spend ~1.3 ms in dispatch and set-up when everything else is masked out -- took 7.95 ms against 6.97: the
         // loop state costs 17 spilled registers at the 168 the occupancy allows, and the same body with one slot per
         // workgroup already loses 0.45 ms to them.)
-        NNGP_REQUIRE(grid < (int64_t)2147483647, "kernel_build: grid too large (%lld workgroups)", (long long)grid);
+        NNGP_TRY(mfma_grid(tiles_r, tiles_c, a.sym, &sup_r, &sup_c, &grid));
         const int ablate = NNGP_KNOB(3) >= 32 && NNGP_KNOB(3) < 40 ? NNGP_KNOB(3) - 32 : 0;  // timing ablations (wrong results)
         const int variant = NNGP_KNOB(5) >= 20 && NNGP_KNOB(5) < 30 ? NNGP_KNOB(5) - 20 : 0;  // A/B timing of the kernel forms
 #define NNGP_K1_LAUNCH(KC_, PF_, WG_, LO_) \

@@ -15,10 +15,7 @@
 //   * every output is written from the float64 sum: float64, float32 (+ the regulariser on its diagonal), the mirror image of an
 //     off-diagonal tile of a symmetric build (transposed through LDS), the float32 copy's lower triangle only when asked.
 // Cost: one map evaluation per group and entry, against one for the plain kernel, plus one read-modify-write of K.
-#include "common.h"
-#include "trig_tab.h"
-#include "f64_math.h"
-#include "act_map.h"
+#include "kernel_tile.h"
 #include <math.h>
 #include <vector>
 
@@ -26,9 +23,7 @@ namespace nngp {
 
 namespace {
 
-constexpr int KT = 64;       // output tile edge
 constexpr int GKC = 8;       // features staged per step
-constexpr int LDP = KT + 2;  // LDS row stride in doubles (every row 16-byte aligned)
 
 struct AddArgs {
     BuildArgs a;           // the caller's build: operands, range, outputs
@@ -117,25 +112,6 @@ __device__ __forceinline__ void group_map(double (&k)[4][4], double (&q1)[4], do
     }
 }
 
-template <typename T>
-__device__ __forceinline__ void store4(T* base, int64_t ld, int64_t i, int64_t j, int64_t i_end, int64_t j_end,
-                                       const double v[4], bool vec_ok) {
-    if (base == nullptr || i >= i_end) return;
-    T* p = base + i * ld + j;
-    if (vec_ok && j + 3 < j_end) {
-        if constexpr (sizeof(T) == 8) {
-            reinterpret_cast<double2*>(p)[0] = make_double2(v[0], v[1]);
-            reinterpret_cast<double2*>(p)[1] = make_double2(v[2], v[3]);
-        } else {
-            reinterpret_cast<float4*>(p)[0] = make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
-        }
-    } else {
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-            if (j + c < j_end) p[c] = (T)v[c];
-    }
-}
-
 // NTK: the Theta outputs are wanted too (otherwise the NTK chain is dead code and its sums take no registers).
 template <bool NTK>
 __global__ __launch_bounds__(256) void k_build_add(AddArgs p, ArchDev arch, int64_t tiles_c, int vec_ok) {
@@ -149,11 +125,7 @@ __global__ __launch_bounds__(256) void k_build_add(AddArgs p, ArchDev arch, int6
     const int tx = tid & 15, ty = tid >> 4;
     int64_t bi, bj;
     if (a.sym) {
-        const int64_t b = blockIdx.x;
-        bi = (int64_t)((sqrt(8.0 * (double)b + 1.0) - 1.0) * 0.5);
-        while (bi * (bi + 1) / 2 > b) --bi;
-        while ((bi + 1) * (bi + 2) / 2 <= b) ++bi;
-        bj = b - bi * (bi + 1) / 2;
+        lower_tile(blockIdx.x, &bi, &bj);
     } else {
         bi = blockIdx.x / tiles_c;
         bj = blockIdx.x % tiles_c;
@@ -272,50 +244,9 @@ __global__ __launch_bounds__(256) void k_build_add(AddArgs p, ArchDev arch, int6
                 if (NTK && p.full_t != nullptr) st[r][c] = fma(w0, p.full_t[gi * p.ldf + gj + c], st[r][c]);
             }
         }
-        store4(a.nngp64, a.ld64, gi, gj, i_end, j_end, sn[r], vec);
-        if (NTK) store4(a.ntk64, a.ld64, gi, gj, i_end, j_end, st[r], vec);
-        if (a.nngp32 != nullptr || (NTK && a.ntk32 != nullptr)) {  // float32 copies (factorisation input): regulariser on the diagonal
-            double vn[4], vt[4];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const bool diag = a.sym && gi == gj + c;
-                vn[c] = sn[r][c] + (diag ? a.diag_add_nngp32 : 0.0);
-                vt[c] = NTK ? st[r][c] + (diag ? a.diag_add_ntk32 : 0.0) : 0.0;
-            }
-            store4(a.nngp32, a.ld32, gi, gj, i_end, j_end, vn, vec);
-            if (NTK) store4(a.ntk32, a.ld32, gi, gj, i_end, j_end, vt, vec);
-        }
+        tile_store_4x4<NTK>(a, i0, j0, r, sn, st, vec);
     }
-
-    // ---- mirror image of an off-diagonal tile (symmetric build): transpose through LDS ----
-    if (a.sym && bi != bj) {
-        for (int which = 0; which < (NTK ? 2 : 1); ++which) {
-            if (which == 0 && a.nngp64 == nullptr && a.nngp32 == nullptr) continue;
-            if (which == 1 && a.ntk64 == nullptr && a.ntk32 == nullptr) continue;
-            __syncthreads();
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) smem[(tx * 4 + c) * LDP + ty + 16 * r] = which == 0 ? sn[r][c] : st[r][c];
-            __syncthreads();
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                double v[4];
-                const double2 v01 = *reinterpret_cast<const double2*>(&smem[(ty + 16 * r) * LDP + tx * 4]);
-                const double2 v23 = *reinterpret_cast<const double2*>(&smem[(ty + 16 * r) * LDP + tx * 4 + 2]);
-                v[0] = v01.x; v[1] = v01.y; v[2] = v23.x; v[3] = v23.y;
-                // element (j0 + ty + 16 r, i0 + tx * 4 + c); rows bounded by n2 (= n1), columns by row_end
-                const int64_t mi = j0 + ty + 16 * r, mj = i0 + tx * 4;
-                if (which == 0) {
-                    store4(a.nngp64, a.ld64, mi, mj, j_end, i_end, v, vec);
-                    if (!a.lower32) store4(a.nngp32, a.ld32, mi, mj, j_end, i_end, v, vec);
-                } else {
-                    store4(a.ntk64, a.ld64, mi, mj, j_end, i_end, v, vec);
-                    if (!a.lower32) store4(a.ntk32, a.ld32, mi, mj, j_end, i_end, v, vec);
-                }
-            }
-        }
-    }
+    if (a.sym && bi != bj) tile_mirror_4x4<NTK>(a, i0, j0, smem, sn, st, vec);
 }
 
 // K's diagonal of the summed kernel, one row per thread: sum_g w_g diag(q_g) in the table's order, then the whole-input term from
@@ -340,15 +271,7 @@ __global__ __launch_bounds__(256) void k_diag_add(const double* __restrict__ x, 
             k = s * (1.0 / (double)(ke - kb));
         }
         double t = 0.0;
-        for (int l = 0; l < arch.n_dense; ++l) {
-            k = fma(arch.w2[l], k, arch.b2[l]);
-            t = fma(arch.w2[l], t, k);
-            if (l < arch.n_dense - 1) {
-                double kd;
-                act_diag(arch.act[l], arch.ap[l], k, tab, k, kd);
-                t *= kd;
-            }
-        }
+        diag_chain_act(arch, tab, k, t);
         const double w = full ? gr.full_weight : gr.weight[g];
         sn = fma(w, k, sn);
         st = fma(w, t, st);
@@ -427,19 +350,11 @@ int launch_kernel_build_additive(const BuildArgs& a, const ArchDev& arch, hipStr
     const GroupsDev& g = *arch.groups;
     ArchDev plain = arch;
     plain.groups = nullptr;
-    const int64_t rows = a.row_end - a.row_begin;
-    if (rows <= 0 || a.n2 <= 0) return 0;
-    NNGP_REQUIRE(a.d > 0, "kernel_build: d must be positive");
     const bool want_n = a.nngp64 != nullptr || a.nngp32 != nullptr, want_t = a.ntk64 != nullptr || a.ntk32 != nullptr;
-    const int64_t tiles_r = (rows + KT - 1) / KT, tiles_c = (a.n2 + KT - 1) / KT;
-    int64_t nblocks;
-    if (a.sym) {
-        NNGP_REQUIRE(a.row_begin == 0 && a.row_end == a.n1 && a.n1 == a.n2, "kernel_build: symmetric mode needs the full row range");
-        nblocks = tiles_r * (tiles_r + 1) / 2;
-    } else {
-        nblocks = tiles_r * tiles_c;
-    }
-    NNGP_REQUIRE(nblocks < (int64_t)2147483647, "kernel_build: grid too large (%lld tiles)", (long long)nblocks);
+    int64_t tiles_r, tiles_c, nblocks;
+    int vec_ok;
+    NNGP_TRY(plan_build_tiles(a, false, &tiles_r, &tiles_c, &nblocks, &vec_ok));
+    if (nblocks == 0) return 0;
 
     // 1. the whole-input term in float64: into the float64 outputs themselves, or into scratch when a wanted kernel has none
     AddArgs p{};
@@ -470,13 +385,6 @@ int launch_kernel_build_additive(const BuildArgs& a, const ArchDev& arch, hipStr
     }
 
     // 2. the group sum, added in float64; every output from the sum
-    auto aligned = [](const void* q, int64_t ld, int esz) {
-        return q == nullptr || ((((uintptr_t)q) & 15) == 0 && ((ld * esz) & 15) == 0);
-    };
-    // 16-byte stores: every row start aligned for every output in use (columns start at multiples of 4; the mirror's columns are
-    // rows of a symmetric build, which starts at row 0)
-    const int vec_ok = aligned(a.nngp64, a.ld64, 8) && aligned(a.ntk64, a.ld64, 8) && aligned(a.nngp32, a.ld32, 4) &&
-                       aligned(a.ntk32, a.ld32, 4);
     if (want_t)
         hipLaunchKernelGGL(k_build_add<true>, dim3((unsigned)nblocks), dim3(256), 0, s, p, plain, tiles_c, vec_ok);
     else

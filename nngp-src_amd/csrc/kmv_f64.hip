@@ -1,9 +1,9 @@
 // The matrix-free NNGP operator: OUT = (K(X, X) + diag_add I) V for a block of r vectors, K never written to memory.
 //
-//   k_kmv_f64      one workgroup owns a 64-column block of K and a contiguous range of 64-row tiles.  Per tile it repeats the body of
-//                  the kernel build (k_build_mfma in kernel_build.hip: the X panels staged through LDS in k-chunks of 16, the Gram
-//                  block on v_mfma_f64_16x16x4_f64, the layer recursion in the accumulator layout through the same device functions:
-//                  fast_sqrt_pos / pi_minus_atan2 for ReLU, act_cross / act_diag for the others, the closed-form diagonal) and then
+//   k_kmv_f64      one workgroup owns a 64-column block of K and a contiguous range of 64-row tiles.  Per tile it calls the pieces
+//                  of the kernel build (kernel_tile.h, the ones k_build_mfma of kernel_build.hip is made of: gram_mfma_64 stages
+//                  the X panels through LDS in k-chunks of 16 and forms the Gram block on v_mfma_f64_16x16x4_f64; relu_block_map /
+//                  gen_block_map run the layer recursion in the accumulator layout, without the NTK chain; stage_layer_q) and then
 //                  multiplies the finished block into the vectors without moving it: the C/D layout of the float64 MFMA is
 //                  col = lane & 15, row = (lane >> 4) + 4 reg, and its B operand is one value per lane at (k = lane >> 4,
 //                  col = lane & 15), so register `reg` of a finished 16 x 16 block IS the operand B[k][j] = K[4 reg + k][j].  With
@@ -17,9 +17,7 @@
 // split is a function of n alone, each vector's sums never see another vector (one MFMA output column each), so a vector's result
 // does not depend on r, on its position in the block or on the pass width, and two calls give the same bytes.
 #include "sparse_gp.h"
-#include "trig_tab.h"
-#include "f64_math.h"
-#include "act_map.h"
+#include "kernel_tile.h"
 #include "kmv_f64.h"
 
 #include <cmath>
@@ -28,12 +26,10 @@ namespace nngp {
 
 namespace {
 
-constexpr int KT = 64;         // tile edge
 constexpr int MKC = 16;        // k-chunk of the Gram product
-constexpr int MLD = MKC + 2;   // LDS row stride of the X panels (as in k_build_mfma)
+constexpr int MLD = panel_ld(MKC);
 constexpr int VLD = KT + 2;    // LDS row stride of the V tile: lanes (l16, lg) read word 2 l16 + lg -- distinct banks per half-wave
 constexpr int kKmvTargetGroups = 2048;  // workgroups wanted when the column blocks alone are fewer
-typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 struct KmvArgs {
     const double* x;
@@ -53,13 +49,10 @@ template <int RB, bool GEN>
 __global__ __launch_bounds__(256, 2) void k_kmv_f64(KmvArgs a, ArchDev arch) {
     constexpr int W = 16 * RB;
     constexpr int RI = RB == 1 ? 4 : 2;  // entries of a block whose maps are evaluated side by side (the wide form has fewer registers to spare)
-    constexpr int NLD = MKC * 64 / 256;
     __shared__ __attribute__((aligned(16))) double smem[2 * KT * MLD + W * VLD];  // As | Bs | Vs; the wave sums afterwards
     __shared__ __attribute__((aligned(16))) double tab[65 * 4];
-    __shared__ double qs[GEN ? (NNGP_MAX_DENSE - 1) * 2 * KT : 1];  // [layer][64 rows | 64 columns], before the activation
+    __shared__ double qs[GEN ? (NNGP_MAX_DENSE - 1) * 2 * KT : 1];  // stage_layer_q
     static_assert(RB * 1024 <= 2 * KT * MLD + W * VLD, "the wave sums alias the staging buffers");
-    double* As = smem;
-    double* Bs = smem + KT * MLD;
     double* Vs = smem + 2 * KT * MLD;  // [W][VLD]
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
@@ -103,65 +96,13 @@ __global__ __launch_bounds__(256, 2) void k_kmv_f64(KmvArgs a, ArchDev arch) {
         if constexpr (GEN) {  // read after the k-loop's first barrier
             if (tid < 2 * KT) {
                 const int64_t gq = tid < KT ? i0 + tid : j0 + tid - KT;
-                double q = gq < n ? a.q[gq] : 0.0;
-                for (int l = 0; l < arch.n_dense - 1; ++l) {
-                    double unused;
-                    q = fma(arch.w2[l], q, arch.b2[l]);
-                    qs[l * 2 * KT + tid] = q;
-                    act_diag(arch.act[l], arch.ap[l], q, &kTrigTab[0][0], q, unused);
-                }
+                stage_layer_q(gq < n ? a.q[gq] : 0.0, arch, qs);
             }
         }
 
-        // ---- the Gram block, as in k_build_mfma<16, true, ...> ----
+        // ---- the Gram block of k_build_mfma<16, true, ...> ----
         f64x4 acc[2][2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.0;
-        double ra[NLD], rb[NLD];
-        auto load_chunk = [&](int k0) {  // 64 rows x MKC k per operand, lanes along k
-#pragma unroll
-            for (int e = 0; e < NLD; ++e) {
-                const int idx = tid + 256 * e;
-                const int kk = idx & (MKC - 1), row = idx / MKC;
-                const int kg = k0 + kk;
-                const int64_t gi = i0 + row, gj = j0 + row;
-                ra[e] = (kg < a.d && gi < n) ? a.x[gi * a.d + kg] : 0.0;
-                rb[e] = (kg < a.d && gj < n) ? a.x[gj * a.d + kg] : 0.0;
-            }
-        };
-        load_chunk(0);
-        for (int k0 = 0; k0 < a.d; k0 += MKC) {
-#pragma unroll
-            for (int e = 0; e < NLD; ++e) {
-                const int idx = tid + 256 * e;
-                const int kk = idx & (MKC - 1), row = idx / MKC;
-                As[row * MLD + kk] = ra[e];
-                Bs[row * MLD + kk] = rb[e];
-            }
-            __syncthreads();
-            if (k0 + MKC < a.d) load_chunk(k0 + MKC);
-#pragma unroll
-            for (int ks = 0; ks < MKC / 8; ++ks) {
-                double2 fa[2], fb[2];
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    fa[i] = *reinterpret_cast<const double2*>(&As[(wm * 32 + i * 16 + l16) * MLD + ks * 8 + 2 * lg]);
-                    fb[i] = *reinterpret_cast<const double2*>(&Bs[(wn * 32 + i * 16 + l16) * MLD + ks * 8 + 2 * lg]);
-                }
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[i].x, fb[j].x, acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[i].y, fb[j].y, acc[i][j], 0, 0, 0);
-                    }
-            }
-            __syncthreads();
-        }
+        gram_mfma_64<MKC, true>(PanelRows{a.x, i0, n}, PanelRows{a.x, j0, n}, a.d, a.d, smem, acc);
 
         // ---- layer recursion in the accumulator layout, then the product: entry (row 16 i + lg + 4 r, col 16 j + l16) ----
         const int64_t wi0 = i0 + wm * 32;
@@ -186,49 +127,15 @@ __global__ __launch_bounds__(256, 2) void k_kmv_f64(KmvArgs a, ArchDev arch) {
                     dg[r] = diag_tile && i == j && lg + 4 * r == l16;
                     kv[j][r] = dg[r] ? q1v[r] : av[r] * inv_d;  // exact diagonal: q q' - k^2 == 0 must hold exactly
                 }
-#pragma unroll
-                for (int rh = 0; rh < 4; rh += RI) {
-                    if constexpr (GEN) {
-                        for (int l = 0; l < arch.n_dense; ++l) {
-                            const double w2 = arch.w2[l], b2 = arch.b2[l];
-                            const bool hidden = l < arch.n_dense - 1;
-                            const int code = hidden ? arch.act[l] : NNGP_ACT_RELU;
-                            const double* ap = arch.ap[hidden ? l : 0];
-                            const double q2l = hidden ? qs[l * 2 * KT + KT + wn * 32 + j * 16 + l16] : 0.0;
-#pragma unroll
-                            for (int r = rh; r < rh + RI; ++r) {
-                                double k = fma(w2, kv[j][r], b2);
-                                if (hidden) {
-                                    double kd;
-                                    if (dg[r]) act_diag(code, ap, k, tab, k, kd);  // theta = 0 exactly, as in k_diag_from_q_act
-                                    else act_cross(code, ap, k, qs[l * 2 * KT + wm * 32 + i * 16 + lg + 4 * r], q2l, tab, k, kd);
-                                }
-                                kv[j][r] = k;
-                            }
-                        }
-                    } else {
-                        double q2v = q2in[j];
-                        for (int l = 0; l < arch.n_dense; ++l) {
-                            const double w2 = arch.w2[l], b2 = arch.b2[l];
-                            const bool relu = l < arch.n_dense - 1;
-                            q2v = fma(w2, q2v, b2);
-#pragma unroll
-                            for (int r = rh; r < rh + RI; ++r) {
-                                q1v[r] = fma(w2, q1v[r], b2);
-                                double k = fma(w2, kv[j][r], b2);
-                                if (relu) {
-                                    const double rr = dg[r] ? 0.0 : fma(q1v[r], q2v, -k * k);
-                                    const double s = rr > 0.0 ? fast_sqrt_pos(rr > 0.0 ? rr : 1.0) : 0.0;
-                                    double kd = pi_minus_atan2(s, k, tab) * (0.5 / kPi);
-                                    kd = dg[r] ? 0.5 : kd;  // theta = 0 on the diagonal, exactly
-                                    k = fma(kd, k, s * (0.5 / kPi));
-                                }
-                                kv[j][r] = k;
-                                q1v[r] *= 0.5;
-                            }
-                            q2v *= 0.5;
-                        }
-                    }
+                // the build's maps without the NTK chain (tnone is never touched), RI entries side by side
+                double tnone[4];
+                if constexpr (GEN) {
+                    const int row0 = wm * 32 + i * 16 + lg, col = KT + wn * 32 + j * 16 + l16;
+                    gen_block_map<false, 0, RI>(arch, tab, qs, row0, col, kv[j], tnone, dg);
+                    if constexpr (RI == 2) gen_block_map<false, 2, 2>(arch, tab, qs, row0, col, kv[j], tnone, dg);
+                } else {
+                    relu_block_map<false, 0, RI>(arch, true, tab, kv[j], tnone, q1v, q2in[j], dg);
+                    if constexpr (RI == 2) relu_block_map<false, 2, 2>(arch, true, tab, kv[j], tnone, q1v, q2in[j], dg);
                 }
                 // entries outside the matrix take no part (their V is zero, but the map of a zero row need not be finite)
                 const bool col_ok = wj0 + j * 16 + l16 < n;

@@ -78,6 +78,28 @@ def test_operator_on_identity_columns_meets_the_angle_gate(name, family):
     np.testing.assert_array_equal(shifted, out + 0.375 * np.eye(n))
 
 
+@pytest.mark.parametrize("name", ["relu1", "relu2_bias", "erf_abc"])
+@pytest.mark.parametrize("family", ["d2", "d16"])
+def test_operator_and_build_run_one_map(name, family):
+    """OUT of the identity (diag_add = 0) has the stored build's bits on the lower triangle (row >= column).  Those entries come
+    from the same tile with the same operand roles in both kernels, through the one Gram loop and layer map of kernel_tile.h, and
+    a one-hot vector makes the second MFMA, the wave sum and the split reduction exact (each is k * 1 + 0).  None of these nets
+    takes the composite map in the build."""
+    net = A.cases()[name][0]
+    x, _, _ = A.block(family, "sym", net)
+    n = x.shape[0]
+    if net.family == "relu":
+        k = G.kernel_build(x, None, net.w_std, net.b_std, get=("nngp",))["nngp"]
+    else:
+        k = G.build_act(x, None, net.w_std, net.b_std, net.acts, get=("nngp",))["nngp"]
+    out, rc = kmv(x, np.eye(n), net.w_std, net.b_std, net.acts)
+    assert rc == 0 and out.shape == k.shape
+    low = np.tril_indices(n)
+    differ = out[low] != k[low]
+    print("%s %s: n %d, %d of %d lower entries differ from the build" % (name, family, n, int(differ.sum()), differ.size))
+    assert np.array_equal(out[low], k[low])
+
+
 # ---- 2. the operator against the stored build ----
 
 NETS = {"relu1": ([1.0, 1.0], [0.0, 0.0], None), "relu3": ([1.3] * 4, [0.0] * 4, None), "bias2": ([1.4] * 3, [0.25] * 3, None),
