@@ -84,6 +84,8 @@ I8S_ABI_SYMBOLS = ("nngp_i8s_cut_rows", "nngp_i8s_cut_sym", "nngp_i8s_residual")
 # include/nngp_matfree.h: the matrix-free exact NNGP posterior and its fused K.V operator; GPU library only (no host build)
 MATFREE_ABI_SYMBOLS = ("nngp_matfree_create", "nngp_matfree_destroy", "nngp_matfree_fit", "nngp_matfree_solve",
                        "nngp_matfree_predict", "nngp_matfree_alpha", "nngp_matfree_info", "nngp_kmv_f64")
+# include/nngp_matfree_additive.h: the matrix-free model and its operator on the additive kernel over feature groups
+MATFREE_ADDITIVE_ABI_SYMBOLS = ("nngp_matfree_create_additive", "nngp_kmv_additive_f64")
 BOUND_DTC, BOUND_VFE = 0, 1
 BOUNDS = {"dtc": BOUND_DTC, "vfe": BOUND_VFE}
 
@@ -161,6 +163,7 @@ def load(knobs: bool = False):
     bind_sparse_ard_prototypes(lib)
     bind_i8s_prototypes(lib)
     bind_matfree_prototypes(lib)
+    bind_matfree_additive_prototypes(lib)
     _libs[knobs] = lib
     return lib
 
@@ -410,6 +413,17 @@ def bind_matfree_prototypes(lib):
     lib.nngp_matfree_info.argtypes = [vp, ctypes.POINTER(NngpMatfreeInfo)]
     lib.nngp_kmv_f64.argtypes = [vp, i64, vp, i64, i32, vp, i64, i32, archp, dbl, vp]
     for name in MATFREE_ABI_SYMBOLS:
+        getattr(lib, name).restype = ctypes.c_int
+    return lib
+
+
+def bind_matfree_additive_prototypes(lib):
+    """Argument and result types of include/nngp_matfree_additive.h (the HIP library only)."""
+    vp, i64, i32, dbl = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_double
+    archp, groupsp = ctypes.POINTER(NngpArchAct), ctypes.POINTER(NngpGroups)
+    lib.nngp_matfree_create_additive.argtypes = [ctypes.POINTER(vp), i64, i64, i64, i64, i32, i32, archp, groupsp, dbl, i32, dbl]
+    lib.nngp_kmv_additive_f64.argtypes = [vp, i64, vp, i64, i32, vp, i64, i32, archp, groupsp, dbl, vp]
+    for name in MATFREE_ADDITIVE_ABI_SYMBOLS:
         getattr(lib, name).restype = ctypes.c_int
     return lib
 

@@ -5,7 +5,8 @@
 // float32 outputs are asked for).  k_build_add then computes, one 64 x 64 tile per 256-thread workgroup and 4 x 4 entries per
 // thread, the group sum on the float64 VALU and adds it to that result in float64:
 //   * a group's Gram entries x_g . x'_g are as short as one or two products, so they are accumulated from row slices staged in
-//     LDS (k-chunks of 8, the next chunk's global loads in flight while the current one is consumed) -- no padded MFMA;
+//     LDS (k-chunks of 8, the next chunk's global loads in flight while the current one is consumed) -- no padded MFMA
+//     (group_walk of kernel_tile.h, shared with the matrix-free operator's additive form);
 //   * the two diagonal entries |x_g|^2, |x'_g|^2 of every entry come from the SAME staged values in the SAME order of
 //     operations as the Gram entry.  Two rows whose slice is bit-identical (untouched default predicates: the common case) then
 //     give k == q == q' bit for bit and are taken through the diagonal form of the map (theta = 0 exactly), instead of a square
@@ -23,8 +24,6 @@ namespace nngp {
 
 namespace {
 
-constexpr int GKC = 8;       // features staged per step
-
 struct AddArgs {
     BuildArgs a;           // the caller's build: operands, range, outputs
     const double* full_n;  // the whole-input term, float64, indexed like the outputs (NULL: full_weight == 0 or not wanted)
@@ -33,92 +32,11 @@ struct AddArgs {
     GroupsDev g;
 };
 
-// lo with hi + lo = w2 * x + b2 to twice the working precision, for hi = fma(w2, x, b2): the product's and the sum's rounding
-// errors, exactly (two-product by fma, two-sum), plus what the fma's single rounding left of them.
-__device__ __forceinline__ double affine_lo(double w2, double x, double b2, double hi) {
-    const double p = w2 * x, ep = fma(w2, x, -p);
-    const double s = p + b2, bb = s - p;
-    const double es = (p - (s - bb)) + (b2 - bb);
-    return (s - hi) + (ep + es);
-}
-
-// act_cross of an Erf layer (act_map.h) with the bracket q1 q2 - k^2 taken from k, q1, q2 as hi + lo pairs.  A group's slices are
-// nearly parallel far more often than whole rows are, and then r = 1 + 2 b^2 (q1 + q2) + 4 b^4 (q1 q2 - k^2) is left with
-// r ~ 4 b^2 q while one rounding of the Dense layer's affine map is worth 4 b^4 u q^2 of it: at raw forest norms (q ~ 6e5) that is
-// 5e-11 of Theta.  The first-order terms of the lo parts remove it (the operations on the hi parts are act_cross's own).
-__device__ __forceinline__ void erf_cross_comp(const double* ap, double k, double kl, double q1, double q1l, double q2, double q2l,
-                                               const double* __restrict__ tab, double& ko, double& kd) {
-    const double kk = k * k;
-    const double lo = fma(q1, q2l, fma(q2, q1l, -2.0 * (k * kl)));
-    const double br = fmax((fma(q1, q2, -kk) + fma(-k, k, kk)) + lo, 0.0);
-    const double w = fast_sqrt_pos(fma(ap[1] * ap[1], br, fma(ap[1], q1 + q2, 1.0)));
-    ko = fma(ap[0], pi_minus_atan2(w, ap[1] * k, tab) - 0.5 * kPi, ap[2]);
-    kd = ap[3] * fast_rcp(w);
-}
-
-// One group's term of a thread's 4 x 4 entries through Dense, (act, Dense)*: k[r][c] the Gram entries, q1[r] / q2[c] the diagonal
-// entries of its rows / columns, all already normalised.  The layers are the outer loop, so a layer's map of the 4 + 4 diagonal
-// entries runs once per thread and not once per entry.  same: k == q1 == q2 bit for bit (identical slices) -- the diagonal form.
-template <bool NTK>
-__device__ __forceinline__ void group_map(double (&k)[4][4], double (&q1)[4], double (&q2)[4], const ArchDev& arch,
-                                          const double* __restrict__ tab, double (&t)[4][4]) {
-    bool same[4][4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            same[r][c] = (q1[r] == k[r][c]) && (q2[c] == k[r][c]);
-            t[r][c] = 0.0;
-        }
-    for (int l = 0; l < arch.n_dense; ++l) {
-        const double w2 = arch.w2[l], b2 = arch.b2[l];
-        const bool hidden = l < arch.n_dense - 1;
-        const int code = hidden ? arch.act[l] : NNGP_ACT_RELU;
-        const bool erf = hidden && code == NNGP_ACT_ERF;
-        const double* ap = arch.ap[hidden ? l : 0];
-        double q1l[4], q2l[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const double a = q1[e], b = q2[e];
-            q1[e] = fma(w2, a, b2);
-            q2[e] = fma(w2, b, b2);
-            q1l[e] = erf ? affine_lo(w2, a, b2, q1[e]) : 0.0;
-            q2l[e] = erf ? affine_lo(w2, b, b2, q2[e]) : 0.0;
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                double kk = fma(w2, k[r][c], b2);
-                double tt = NTK ? fma(w2, t[r][c], kk) : 0.0;
-                if (hidden) {
-                    double kd;
-                    if (same[r][c]) act_diag(code, ap, kk, tab, kk, kd);
-                    else if (erf) erf_cross_comp(ap, kk, affine_lo(w2, k[r][c], b2, kk), q1[r], q1l[r], q2[c], q2l[c], tab, kk, kd);
-                    else act_cross(code, ap, kk, q1[r], q2[c], tab, kk, kd);
-                    tt *= kd;
-                }
-                k[r][c] = kk;
-                t[r][c] = tt;
-            }
-        if (hidden) {
-            double unused;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                act_diag(code, ap, q1[e], tab, q1[e], unused);
-                act_diag(code, ap, q2[e], tab, q2[e], unused);
-            }
-        }
-    }
-}
-
 // NTK: the Theta outputs are wanted too (otherwise the NTK chain is dead code and its sums take no registers).
 template <bool NTK>
 __global__ __launch_bounds__(256) void k_build_add(AddArgs p, ArchDev arch, int64_t tiles_c, int vec_ok) {
     __shared__ __attribute__((aligned(16))) double smem[KT * LDP];  // As | Bs while the groups are walked, T for the mirror
     __shared__ __attribute__((aligned(16))) double tab[65 * 4];
-    double* As = smem;               // [GKC][LDP]
-    double* Bs = smem + GKC * LDP;   // [GKC][LDP]
     const BuildArgs& a = p.a;
 
     const int tid = threadIdx.x;
@@ -134,101 +52,22 @@ __global__ __launch_bounds__(256) void k_build_add(AddArgs p, ArchDev arch, int6
     const int64_t i_end = a.row_end, j_end = a.n2;
     for (int i = tid; i < 65 * 4; i += 256) tab[i] = kTrigTab[i >> 2][i & 3];  // read after the first barrier below
 
-    double sn[4][4], st[4][4], acc[4][4], qa[4], qb[4];
+    // the group sum, in the table's order, in float64 registers (group_walk of kernel_tile.h; tab is read after its first barrier)
+    double sn[4][4], st[4][4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        qa[r] = 0.0;
-        qb[r] = 0.0;
+    for (int r = 0; r < 4; ++r)
 #pragma unroll
-        for (int c = 0; c < 4; ++c) sn[r][c] = st[r][c] = acc[r][c] = 0.0;
-    }
-
-    // The (group, k-chunk) steps form one flat sequence; the global loads of step s + 1 are issued into registers before step s
-    // is consumed from LDS, so their latency hides behind the FMAs and the layer map of the group that has just ended.
-    const int G = p.g.n_groups;
-    double ra[2], rb[2];
-    auto load_chunk = [&](int k0, int k_end) {  // 64 rows x GKC features per operand; features past the group's end are zero
+        for (int c = 0; c < 4; ++c) sn[r][c] = st[r][c] = 0.0;
+    group_walk<NTK>(GroupLay4x4{}, PanelRows{a.x1, i0, i_end}, PanelRows{a.x2, j0, j_end}, a.d, p.g, arch, tab, smem,
+                    [&](double wg, const double (&k)[4][4], const double (&t)[4][4]) {
 #pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const int idx = tid + 256 * e;
-            const int kk = idx & (GKC - 1), row = idx >> 3;
-            const int kg = k0 + kk;
-            const int64_t gi = i0 + row, gj = j0 + row;
-            ra[e] = (kg < k_end && gi < i_end) ? a.x1[gi * a.d + kg] : 0.0;
-            rb[e] = (kg < k_end && gj < j_end) ? a.x2[gj * a.d + kg] : 0.0;
-        }
-    };
-    int g = 0, k0 = 0, k_begin = 0, k_end = 0;
-    if (G > 0) {
-        k_begin = p.g.begin[0];
-        k_end = p.g.end[0];
-        k0 = k_begin;
-        load_chunk(k0, k_end);
-    } else {
-        __syncthreads();  // tab
-    }
-    while (g < G) {
+                        for (int r = 0; r < 4; ++r)
 #pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const int idx = tid + 256 * e;
-            const int kk = idx & (GKC - 1), row = idx >> 3;
-            As[kk * LDP + row] = ra[e];
-            Bs[kk * LDP + row] = rb[e];
-        }
-        __syncthreads();
-        // the step after this one
-        int ng = g, nk0 = k0 + GKC, nk_begin = k_begin, nk_end = k_end;
-        if (nk0 >= k_end) {
-            ng = g + 1;
-            if (ng < G) {
-                nk_begin = p.g.begin[ng];
-                nk_end = p.g.end[ng];
-                nk0 = nk_begin;
-            }
-        }
-        if (ng < G) load_chunk(nk0, nk_end);
-        const int kn = (k_end - k0) < GKC ? (k_end - k0) : GKC;
-        for (int kk = 0; kk < kn; ++kk) {
-            double av[4], bv[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) av[r] = As[kk * LDP + ty + 16 * r];
-            const double2 b01 = *reinterpret_cast<const double2*>(&Bs[kk * LDP + tx * 4]);
-            const double2 b23 = *reinterpret_cast<const double2*>(&Bs[kk * LDP + tx * 4 + 2]);
-            bv[0] = b01.x; bv[1] = b01.y; bv[2] = b23.x; bv[3] = b23.y;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                qa[r] = fma(av[r], av[r], qa[r]);
-                qb[r] = fma(bv[r], bv[r], qb[r]);
-#pragma unroll
-                for (int c = 0; c < 4; ++c) acc[r][c] = fma(av[r], bv[c], acc[r][c]);
-            }
-        }
-        __syncthreads();
-        if (ng != g) {  // the group is complete: its term of every entry
-            const double inv_dg = 1.0 / (double)(k_end - k_begin);
-            const double wg = p.g.weight[g];
-            double tv[4][4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                qa[r] *= inv_dg;
-                qb[r] *= inv_dg;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) acc[r][c] *= inv_dg;
-            }
-            group_map<NTK>(acc, qa, qb, arch, tab, tv);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                qa[r] = qb[r] = 0.0;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    sn[r][c] = fma(wg, acc[r][c], sn[r][c]);
-                    if (NTK) st[r][c] = fma(wg, tv[r][c], st[r][c]);
-                    acc[r][c] = 0.0;
-                }
-            }
-        }
-        g = ng; k0 = nk0; k_begin = nk_begin; k_end = nk_end;
-    }
+                            for (int c = 0; c < 4; ++c) {
+                                sn[r][c] = fma(wg, k[r][c], sn[r][c]);
+                                if (NTK) st[r][c] = fma(wg, t[r][c], st[r][c]);
+                            }
+                    });
 
     // ---- the whole-input term, then every output from the float64 sum ----
     const double w0 = p.g.full_weight;

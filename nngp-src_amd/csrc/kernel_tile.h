@@ -8,6 +8,8 @@
 //   the 32 x 32 block at (32 wm, 32 wn) as 2 x 2 accumulators of v_mfma_f64_16x16x4_f64; register r of block (i, j) is the entry
 //   (row 16 i + lg + 4 r, col 16 j + l16), l16 = lane & 15, lg = lane >> 4.
 //   4 x 4 layout (tile_store_4x4, tile_mirror_4x4): thread (tx, ty) = (tid & 15, tid >> 4) holds rows ty + 16 r, columns 4 tx + c.
+//   The group terms of the additive kernel (group_walk, group_map, affine_lo, erf_cross_comp) run in either layout: k_build_add in
+//   the 4 x 4 one, the additive form of k_kmv_f64 in the MFMA one.
 #pragma once
 #include "gp_f64.h"
 #include "trig_tab.h"
@@ -180,6 +182,231 @@ __device__ __forceinline__ void diag_chain_act(const ArchDev& arch, const double
             act_diag(arch.act[l], arch.ap[l], k, tab, k, kd);
             t *= kd;
         }
+    }
+}
+
+// ---- the group terms of an additive kernel (include/nngp_additive.h): k_build_add and the additive form of k_kmv_f64 ----
+constexpr int GKC = 8;  // features of a group staged per step
+
+// lo with hi + lo = w2 * x + b2 to twice the working precision, for hi = fma(w2, x, b2): the product's and the sum's rounding
+// errors, exactly (two-product by fma, two-sum), plus what the fma's single rounding left of them.
+__device__ __forceinline__ double affine_lo(double w2, double x, double b2, double hi) {
+    const double p = w2 * x, ep = fma(w2, x, -p);
+    const double s = p + b2, bb = s - p;
+    const double es = (p - (s - bb)) + (b2 - bb);
+    return (s - hi) + (ep + es);
+}
+
+// act_cross of an Erf layer (act_map.h) with the bracket q1 q2 - k^2 taken from k, q1, q2 as hi + lo pairs.  A group's slices are
+// nearly parallel far more often than whole rows are, and then r = 1 + 2 b^2 (q1 + q2) + 4 b^4 (q1 q2 - k^2) is left with
+// r ~ 4 b^2 q while one rounding of the Dense layer's affine map is worth 4 b^4 u q^2 of it: at raw forest norms (q ~ 6e5) that is
+// 5e-11 of Theta.  The first-order terms of the lo parts remove it (the operations on the hi parts are act_cross's own).
+__device__ __forceinline__ void erf_cross_comp(const double* ap, double k, double kl, double q1, double q1l, double q2, double q2l,
+                                               const double* __restrict__ tab, double& ko, double& kd) {
+    const double kk = k * k;
+    const double lo = fma(q1, q2l, fma(q2, q1l, -2.0 * (k * kl)));
+    const double br = fmax((fma(q1, q2, -kk) + fma(-k, k, kk)) + lo, 0.0);
+    const double w = fast_sqrt_pos(fma(ap[1] * ap[1], br, fma(ap[1], q1 + q2, 1.0)));
+    ko = fma(ap[0], pi_minus_atan2(w, ap[1] * k, tab) - 0.5 * kPi, ap[2]);
+    kd = ap[3] * fast_rcp(w);
+}
+
+// A thread's NR x NC entries of the tile in the group walk, and how it reads its rows' / columns' values of one staged feature
+// (As / Bs: that feature's 64 rows / columns).  The 4 x 4 layout of the additive build:
+struct GroupLay4x4 {
+    static constexpr int NR = 4, NC = 4;
+    __device__ __forceinline__ void rows(const double* As, double (&av)[4]) const {
+        const int ty = threadIdx.x >> 4;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) av[r] = As[ty + 16 * r];
+    }
+    __device__ __forceinline__ void cols(const double* Bs, double (&bv)[4]) const {
+        const int tx = threadIdx.x & 15;
+        const double2 b01 = *reinterpret_cast<const double2*>(&Bs[tx * 4]);
+        const double2 b23 = *reinterpret_cast<const double2*>(&Bs[tx * 4 + 2]);
+        bv[0] = b01.x; bv[1] = b01.y; bv[2] = b23.x; bv[3] = b23.y;
+    }
+};
+// The MFMA layout: row 4 i + r of the thread is register r of its blocks (i, .), column j the column of its blocks (., j).
+struct GroupLayMfma {
+    static constexpr int NR = 8, NC = 2;
+    __device__ __forceinline__ void rows(const double* As, double (&av)[8]) const {
+        const int wm = threadIdx.x >> 7, lg = (threadIdx.x & 63) >> 4;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) av[e] = As[wm * 32 + (e >> 2) * 16 + lg + 4 * (e & 3)];
+    }
+    __device__ __forceinline__ void cols(const double* Bs, double (&bv)[2]) const {
+        const int wn = (threadIdx.x >> 6) & 1, l16 = threadIdx.x & 15;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) bv[j] = Bs[wn * 32 + j * 16 + l16];
+    }
+};
+
+// One group's term of a thread's NR x NC entries through Dense, (act, Dense)*: k[r][c] the Gram entries, q1[r] / q2[c] the diagonal
+// entries of its rows / columns, all already normalised.  The layers are the outer loop, so a layer's map of the NR + NC diagonal
+// entries runs once per thread and not once per entry.  same: k == q1 == q2 bit for bit (identical slices) -- the diagonal form.
+template <bool NTK, int NR, int NC>
+__device__ __forceinline__ void group_map(double (&k)[NR][NC], double (&q1)[NR], double (&q2)[NC], const ArchDev& arch,
+                                          const double* __restrict__ tab, double (&t)[NR][NC]) {
+    bool same[NR][NC];
+#pragma unroll
+    for (int r = 0; r < NR; ++r)
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            same[r][c] = (q1[r] == k[r][c]) && (q2[c] == k[r][c]);
+            t[r][c] = 0.0;
+        }
+    for (int l = 0; l < arch.n_dense; ++l) {
+        const double w2 = arch.w2[l], b2 = arch.b2[l];
+        const bool hidden = l < arch.n_dense - 1;
+        const int code = hidden ? arch.act[l] : NNGP_ACT_RELU;
+        const bool erf = hidden && code == NNGP_ACT_ERF;
+        const double* ap = arch.ap[hidden ? l : 0];
+        double q1l[NR], q2l[NC];
+#pragma unroll
+        for (int e = 0; e < NR; ++e) {
+            const double a = q1[e];
+            q1[e] = fma(w2, a, b2);
+            q1l[e] = erf ? affine_lo(w2, a, b2, q1[e]) : 0.0;
+        }
+#pragma unroll
+        for (int e = 0; e < NC; ++e) {
+            const double b = q2[e];
+            q2[e] = fma(w2, b, b2);
+            q2l[e] = erf ? affine_lo(w2, b, b2, q2[e]) : 0.0;
+        }
+#pragma unroll
+        for (int r = 0; r < NR; ++r)
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                double kk = fma(w2, k[r][c], b2);
+                double tt = NTK ? fma(w2, t[r][c], kk) : 0.0;
+                if (hidden) {
+                    double kd;
+                    if (same[r][c]) act_diag(code, ap, kk, tab, kk, kd);
+                    else if (erf) erf_cross_comp(ap, kk, affine_lo(w2, k[r][c], b2, kk), q1[r], q1l[r], q2[c], q2l[c], tab, kk, kd);
+                    else act_cross(code, ap, kk, q1[r], q2[c], tab, kk, kd);
+                    tt *= kd;
+                }
+                k[r][c] = kk;
+                t[r][c] = tt;
+            }
+        if (hidden) {
+            double unused;
+#pragma unroll
+            for (int e = 0; e < NR; ++e) act_diag(code, ap, q1[e], tab, q1[e], unused);
+#pragma unroll
+            for (int e = 0; e < NC; ++e) act_diag(code, ap, q2[e], tab, q2[e], unused);
+        }
+    }
+}
+
+// The walk over the groups of the table, in its order, for the tile of row panel pa and column panel pb.  The (group, k-chunk)
+// steps form one flat sequence; the slices are staged through LDS (smem: As | Bs, [GKC][LDP] each) and the global loads of step
+// s + 1 are issued into registers before step s is consumed, so their latency hides behind the FMAs and the layer map of the group
+// that has just ended.  A group's Gram entries and its diagonal entries come from the same staged values by fma chains in feature
+// order, times 1.0 / width.  At the end of each group sink(w_g, k, t) receives the thread's mapped entries (t: the NTK chain,
+// meaningful with NTK).  Contains at least one barrier (the caller's LDS writes before the call are visible to what follows it)
+// and ends with one: the caller may reuse smem at once.
+template <bool NTK, typename Lay, int NS, typename Sink>
+__device__ __forceinline__ void group_walk(const Lay& lay, const PanelRows& pa, const PanelRows& pb, int d, const GroupsDev& gr,
+                                           const ArchDev& arch, const double* __restrict__ tab, double (&smem)[NS], Sink&& sink) {
+    constexpr int NR = Lay::NR, NC = Lay::NC;
+    static_assert(2 * GKC * LDP <= NS, "As | Bs");
+    double* As = smem;              // [GKC][LDP]
+    double* Bs = smem + GKC * LDP;  // [GKC][LDP]
+    const int tid = threadIdx.x;
+    double acc[NR][NC], qa[NR], qb[NC];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+        qa[r] = 0.0;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) acc[r][c] = 0.0;
+    }
+#pragma unroll
+    for (int c = 0; c < NC; ++c) qb[c] = 0.0;
+
+    const int G = gr.n_groups;
+    double ra[2], rb[2];
+    auto load_chunk = [&](int k0, int k_end) {  // 64 rows x GKC features per operand; features past the group's end are zero
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int idx = tid + 256 * e;
+            const int kk = idx & (GKC - 1), row = idx >> 3;
+            const int kg = k0 + kk;
+            const int64_t gi = pa.r0 + row, gj = pb.r0 + row;
+            ra[e] = (kg < k_end && gi < pa.end) ? pa.p[gi * d + kg] : 0.0;
+            rb[e] = (kg < k_end && gj < pb.end) ? pb.p[gj * d + kg] : 0.0;
+        }
+    };
+    int g = 0, k0 = 0, k_begin = 0, k_end = 0;
+    if (G > 0) {
+        k_begin = gr.begin[0];
+        k_end = gr.end[0];
+        k0 = k_begin;
+        load_chunk(k0, k_end);
+    } else {
+        __syncthreads();
+    }
+    while (g < G) {
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int idx = tid + 256 * e;
+            const int kk = idx & (GKC - 1), row = idx >> 3;
+            As[kk * LDP + row] = ra[e];
+            Bs[kk * LDP + row] = rb[e];
+        }
+        __syncthreads();
+        // the step after this one
+        int ng = g, nk0 = k0 + GKC, nk_begin = k_begin, nk_end = k_end;
+        if (nk0 >= k_end) {
+            ng = g + 1;
+            if (ng < G) {
+                nk_begin = gr.begin[ng];
+                nk_end = gr.end[ng];
+                nk0 = nk_begin;
+            }
+        }
+        if (ng < G) load_chunk(nk0, nk_end);
+        const int kn = (k_end - k0) < GKC ? (k_end - k0) : GKC;
+        for (int kk = 0; kk < kn; ++kk) {
+            double av[NR], bv[NC];
+            lay.rows(As + kk * LDP, av);
+            lay.cols(Bs + kk * LDP, bv);
+#pragma unroll
+            for (int c = 0; c < NC; ++c) qb[c] = fma(bv[c], bv[c], qb[c]);
+#pragma unroll
+            for (int r = 0; r < NR; ++r) {
+                qa[r] = fma(av[r], av[r], qa[r]);
+#pragma unroll
+                for (int c = 0; c < NC; ++c) acc[r][c] = fma(av[r], bv[c], acc[r][c]);
+            }
+        }
+        __syncthreads();
+        if (ng != g) {  // the group is complete: its term of every entry
+            const double inv_dg = 1.0 / (double)(k_end - k_begin);
+            const double wg = gr.weight[g];
+            double tv[NR][NC];
+#pragma unroll
+            for (int r = 0; r < NR; ++r) {
+                qa[r] *= inv_dg;
+#pragma unroll
+                for (int c = 0; c < NC; ++c) acc[r][c] *= inv_dg;
+            }
+#pragma unroll
+            for (int c = 0; c < NC; ++c) qb[c] *= inv_dg;
+            group_map<NTK>(acc, qa, qb, arch, tab, tv);
+            sink(wg, acc, tv);
+#pragma unroll
+            for (int r = 0; r < NR; ++r) {
+                qa[r] = 0.0;
+#pragma unroll
+                for (int c = 0; c < NC; ++c) acc[r][c] = 0.0;
+            }
+#pragma unroll
+            for (int c = 0; c < NC; ++c) qb[c] = 0.0;
+        }
+        g = ng; k0 = nk0; k_begin = nk_begin; k_end = nk_end;
     }
 }
 

@@ -28,6 +28,7 @@ struct nngp_matfree {
     double diag_reg = 0.0, jitter = 0.0;
     int absolute = 0;
     nngp_sparse* sp = nullptr;   // the preconditioner's model (m_cap > 0)
+    nngp::GroupsDev groups{};    // additive handle (include/nngp_matfree_additive.h): the table arch.groups points to
 
     int64_t n = 0, m = 0, mp = 0;
     bool fitted = false;
@@ -173,10 +174,14 @@ __global__ __launch_bounds__(256) void k_mf_resid(const double* __restrict__ b, 
 }
 
 // one workgroup per test row: mean[row, y] = B_row . alpha_y;  var[row] = kdiag[row] - B_row . Z_row
+// resid (additive handles): the solver's true residual R = B - A Z.  B . Z + Z . R = 2 B . Z - Z . A Z is the quadratic form whose
+// maximum over Z is B . A^-1 B: its error is second order in Z's, where B . Z alone keeps a first-order term Z . R that CG removes
+// only in exact arithmetic (the Galerkin condition).  The additive kernel's preconditioned solves end after two dozen iterations at
+// variances of 2e-4 .. 2e-3 of K(x, x), and there that term is what is left.
 __global__ __launch_bounds__(256) void k_mf_predict_finish(const double* __restrict__ bt, const double* __restrict__ zt, int64_t ld,
                                                            int64_t n, const double* __restrict__ alpha, int ny,
                                                            const double* __restrict__ kdiag, double* __restrict__ mean,
-                                                           double* __restrict__ var) {
+                                                           double* __restrict__ var, const double* __restrict__ resid) {
     __shared__ double red[256];
     const int64_t row = blockIdx.x;
     const double* br = bt + row * ld;
@@ -190,6 +195,11 @@ __global__ __launch_bounds__(256) void k_mf_predict_finish(const double* __restr
     double s = 0.0;
     for (int64_t i = threadIdx.x; i < n; i += 256) s += br[i] * zt[row * ld + i];
     s = block_sum(s, red);
+    if (resid != nullptr) {
+        double c = 0.0;
+        for (int64_t i = threadIdx.x; i < n; i += 256) c += zt[row * ld + i] * resid[row * ld + i];
+        s += block_sum(c, red);
+    }
     if (threadIdx.x == 0) var[row] = kdiag[row] - s;
 }
 
@@ -201,6 +211,8 @@ void mf_free(nngp_matfree* h) {
     h->host = nullptr;
     if (h->sp) (void)nngp_sparse_destroy(h->sp);
     h->sp = nullptr;
+    groups_destroy(&h->groups);
+    h->arch.groups = nullptr;
 }
 
 int mf_alloc(nngp_matfree* h) {
@@ -345,14 +357,11 @@ using namespace nngp;
 
 extern "C" {
 
-int nngp_matfree_create(nngp_matfree** out, int64_t n_cap, int64_t m_cap, int64_t chunk_rows, int64_t rhs_cap, int32_t d, int32_t ny,
-                        const nngp_arch_act* arch, const nngp_groups* groups, int32_t get, double diag_reg,
-                        int32_t diag_reg_absolute_scale, double jitter) {
-    NNGP_REQUIRE(out != nullptr && arch != nullptr, "matfree_create: NULL argument");
-    *out = nullptr;
-    NNGP_REQUIRE(get == NNGP_GET_NNGP, "matfree_create: only the NNGP kernel has a GP posterior to solve for (get=%d)", get);
-    NNGP_REQUIRE(groups == nullptr || (groups->n_groups == 0 && groups->full_weight == 1.0),
-                 "matfree_create: additive kernels are not supported by the fused operator");
+// groups: NULL, or the table of an additive handle -- the handle's own copy for the operator, the diagonal and the cross build, and
+// the caller's for the sparse handle, which copies it too
+static int mf_create(nngp_matfree** out, int64_t n_cap, int64_t m_cap, int64_t chunk_rows, int64_t rhs_cap, int32_t d, int32_t ny,
+                     const nngp_arch_act* arch, const nngp_groups* groups, double diag_reg, int32_t diag_reg_absolute_scale,
+                     double jitter) {
     NNGP_REQUIRE(n_cap >= 1 && n_cap <= ((int64_t)1 << 26), "matfree_create: n_cap must be in 1 .. 2^26 (n_cap=%lld)", (long long)n_cap);
     NNGP_REQUIRE(m_cap >= 0 && m_cap <= 16384, "matfree_create: m_cap must be in 0 .. 16384 (m_cap=%lld)", (long long)m_cap);
     NNGP_REQUIRE(chunk_rows >= TB && chunk_rows % TB == 0, "matfree_create: chunk_rows must be a positive multiple of %d (chunk_rows=%lld)",
@@ -379,9 +388,16 @@ int nngp_matfree_create(nngp_matfree** out, int64_t n_cap, int64_t m_cap, int64_
     h->diag_reg = diag_reg;
     h->absolute = diag_reg_absolute_scale != 0;
     h->jitter = jitter;
-    int rc = mf_alloc(h);
+    int rc = 0;
+    if (groups != nullptr) {
+        bool plain = false;
+        rc = groups_create(groups, d, &h->groups, &plain);
+        if (rc == 0 && !plain) h->arch.groups = &h->groups;
+    }
+    if (rc == 0) rc = mf_alloc(h);
     if (rc == 0 && m_cap > 0)
-        rc = nngp_sparse_create(&h->sp, m_cap, chunk_rows, TB, d, ny, arch, nullptr, diag_reg, diag_reg_absolute_scale, jitter);
+        rc = nngp_sparse_create(&h->sp, m_cap, chunk_rows, TB, d, ny, arch, h->arch.groups != nullptr ? groups : nullptr, diag_reg,
+                                diag_reg_absolute_scale, jitter);
     if (rc != 0) {
         mf_free(h);
         delete h;
@@ -389,6 +405,26 @@ int nngp_matfree_create(nngp_matfree** out, int64_t n_cap, int64_t m_cap, int64_
     }
     *out = h;
     return 0;
+}
+
+int nngp_matfree_create(nngp_matfree** out, int64_t n_cap, int64_t m_cap, int64_t chunk_rows, int64_t rhs_cap, int32_t d, int32_t ny,
+                        const nngp_arch_act* arch, const nngp_groups* groups, int32_t get, double diag_reg,
+                        int32_t diag_reg_absolute_scale, double jitter) {
+    NNGP_REQUIRE(out != nullptr && arch != nullptr, "matfree_create: NULL argument");
+    *out = nullptr;
+    NNGP_REQUIRE(get == NNGP_GET_NNGP, "matfree_create: only the NNGP kernel has a GP posterior to solve for (get=%d)", get);
+    NNGP_REQUIRE(groups == nullptr || (groups->n_groups == 0 && groups->full_weight == 1.0),
+                 "matfree_create: additive kernels are not supported by the fused operator");
+    return mf_create(out, n_cap, m_cap, chunk_rows, rhs_cap, d, ny, arch, nullptr, diag_reg, diag_reg_absolute_scale, jitter);
+}
+
+int nngp_matfree_create_additive(nngp_matfree** out, int64_t n_cap, int64_t m_cap, int64_t chunk_rows, int64_t rhs_cap, int32_t d,
+                                 int32_t ny, const nngp_arch_act* arch, const nngp_groups* groups, double diag_reg,
+                                 int32_t diag_reg_absolute_scale, double jitter) {
+    NNGP_REQUIRE(out != nullptr && arch != nullptr, "matfree_create: NULL argument");
+    *out = nullptr;
+    NNGP_REQUIRE(groups != nullptr, "groups: the group table is NULL");
+    return mf_create(out, n_cap, m_cap, chunk_rows, rhs_cap, d, ny, arch, groups, diag_reg, diag_reg_absolute_scale, jitter);
 }
 
 int nngp_matfree_destroy(nngp_matfree* h) {
@@ -528,7 +564,7 @@ int nngp_matfree_predict(nngp_matfree* h, const double* x_test, int64_t mt, int3
             }
         }
         hipLaunchKernelGGL(k_mf_predict_finish, dim3((unsigned)rows), dim3(256), 0, s, h->bt, h->zt, np, n, h->alpha, h->ny, h->kd,
-                           mean + r0 * h->ny, diag ? var + r0 : nullptr);
+                           mean + r0 * h->ny, diag ? var + r0 : nullptr, (diag && h->arch.groups != nullptr) ? h->r : nullptr);
         NNGP_HIP_CHECK(hipGetLastError());
     }
     NNGP_HIP_CHECK(hipStreamSynchronize(s));

@@ -20,7 +20,7 @@ class Estimator(object):
     def __init__(self, schema_name: str, data_path: str, train_query_path: str, chunk_size: int = 64,
                  use_aux: bool = False, q_error_threshold: float = 100.0, coef_var_threshold: float = 1.0,
                  encoder=None, kernel_type: str = "nngp", serving: bool = True, groups=None, sparse: int = 0,
-                 sparse_select: str = "greedy", matrix_free: int = 0):
+                 sparse_select: str = "greedy", matrix_free: int = 0, matrix_free_groups=None):
         self.schema_name = schema_name
         self.data_path = data_path
         self.train_query_path = train_query_path
@@ -33,6 +33,10 @@ class Estimator(object):
         self.matrix_free = int(matrix_free)  # matrix_free = M > 0: the exact posterior by PCG with M inducing rows as preconditioner (matfree.py)
         if self.matrix_free > 0 and (self.sparse > 0 or kernel_type != "nngp" or groups is not None):
             raise ValueError("matrix_free > 0 solves the plain NNGP posterior: it needs kernel_type='nngp', no groups, and not sparse")
+        # matrix_free_groups = "pairs" or (begin, end) ranges: the matrix-free model on the additive kernel (matfree_additive.py)
+        self.matrix_free_groups = matrix_free_groups
+        if matrix_free_groups is not None and self.matrix_free <= 0:
+            raise ValueError("matrix_free_groups is the additive kernel of the matrix-free model: it needs matrix_free = M > 0")
         self.serving = serving  # load_model also builds the explicit float64 inverse: predict = one product per batch
         print("loading schema and training data ... This may take seconds ...")
         if encoder is None:
@@ -51,10 +55,13 @@ class Estimator(object):
             self._native = None
         print("Building model kernel ...")
         init_fn, apply_fn, kernel_fn = stax.serial(stax.Dense(512), stax.Relu(), stax.Dense(1))
-        if groups is not None:
-            kernel_fn = kernel_fn.with_groups(groups)
+        if groups is not None or matrix_free_groups is not None:
+            kernel_fn = kernel_fn.with_groups(groups if groups is not None else matrix_free_groups)
         kernel_fn = batch(kernel_fn, device_count=0, batch_size=0)
-        if self.matrix_free > 0:  # fitted here: the preconditioner's sparse fit, then alpha by PCG
+        if self.matrix_free > 0 and matrix_free_groups is not None:  # the same, on the additive kernel (all weights 1)
+            from .matfree_additive import matfree_additive_mse_ensemble
+            self.predict_fn = matfree_additive_mse_ensemble(kernel_fn, self.X_train, self.Y_train, self.matrix_free, diag_reg=1e-3)
+        elif self.matrix_free > 0:  # fitted here: the preconditioner's sparse fit, then alpha by PCG
             from .matfree import matfree_mse_ensemble
             self.predict_fn = matfree_mse_ensemble(kernel_fn, self.X_train, self.Y_train, self.matrix_free, diag_reg=1e-3)
         elif self.sparse > 0:  # fitted here: every training row through the accumulation, once

@@ -4,7 +4,8 @@
 (K + sigma2 I) alpha = y by preconditioned conjugate gradients: K is applied by a fused kernel that builds it tile by tile and
 multiplies it into a block of vectors (``nngp_kmv_f64``), and the sparse model of ``m`` inducing rows is the preconditioner
 (m = 0: none).  The footprint is O(N (d + m + rhs_cap)); means and variances are those of the exact model to the solver's
-tolerance.  NNGP only, the plain kernel only (no feature groups, no input scale), ``cov`` = None or "diag".
+tolerance.  NNGP only, the plain kernel only (no feature groups, no input scale: ``matfree_additive.AdditiveMatrixFreeGPModel``
+has them), ``cov`` = None or "diag".
 """
 from __future__ import annotations
 
@@ -72,7 +73,7 @@ class MatrixFreeGPModel(HasSpec):
                  max_iter: int = 1000, rhs_cap: int = 64, chunk_rows: int = 8192, jitter: float = 1e-8,
                  diag_reg_absolute_scale: bool = False, ny: int = 1, activations=None, input_scale=None, groups=None,
                  group_weights=None, full_weight=1.0, get: str = "nngp", allow_unconverged: bool = False, knobs: bool = False):
-        spec = check_matfree_spec(KernelSpec(w_std, b_std, activations, input_scale, groups, group_weights, full_weight), get)
+        spec = self._check_spec(KernelSpec(w_std, b_std, activations, input_scale, groups, group_weights, full_weight), get)
         chunk_rows = min(int(chunk_rows), -(-int(n_cap) // 128) * 128) if int(n_cap) >= 1 else int(chunk_rows)
         check_matfree_arguments(n_cap, m, chunk_rows, rhs_cap, ny, diag_reg, jitter, tol, max_iter)
         self.spec = spec.resolve(d)
@@ -85,9 +86,23 @@ class MatrixFreeGPModel(HasSpec):
         self.n = 0
         self.inducing = None
         self.handle = ctypes.c_void_p()
-        self._check(self.lib.nngp_matfree_create(ctypes.byref(self.handle), self.n_cap, self.m_cap, self.chunk_rows, self.rhs_cap,
-                                                 self.d, self.ny, ctypes.byref(self.spec.arch_act()), None, _lib.GET_NNGP,
-                                                 float(diag_reg), int(bool(diag_reg_absolute_scale)), float(jitter)))
+        self._check(self._create(float(diag_reg), int(bool(diag_reg_absolute_scale)), float(jitter)))
+
+    # ---- what a model of another kernel gives anew (matfree_additive.py): the spec's check, the create call, the rows' scale and
+    # the kernel_fn that chooses inducing rows when from_kernel_fn kept none ----
+    _check_spec = staticmethod(check_matfree_spec)
+
+    def _create(self, diag_reg, absolute, jitter):
+        return self.lib.nngp_matfree_create(ctypes.byref(self.handle), self.n_cap, self.m_cap, self.chunk_rows, self.rhs_cap, self.d,
+                                            self.ny, ctypes.byref(self.spec.arch_act()), None, _lib.GET_NNGP, diag_reg, absolute,
+                                            jitter)
+
+    def _scaled(self, xd):
+        return xd  # this model takes no input_scale
+
+    def _spec_kernel_fn(self):
+        from . import mll
+        return mll.rebuild_kernel_fn(list(self.spec.w_std), list(self.spec.b_std), self.spec.activations)
 
     @classmethod
     def from_kernel_fn(cls, kernel_fn, n_cap: int, d: int, **kwargs):
@@ -129,8 +144,7 @@ class MatrixFreeGPModel(HasSpec):
     def _select(self, x):
         kernel_fn = self.kernel_fn
         if kernel_fn is None:
-            from . import mll
-            kernel_fn = mll.rebuild_kernel_fn(list(self.spec.w_std), list(self.spec.b_std), self.spec.activations)
+            kernel_fn = self._spec_kernel_fn()
         from .sparse import select_inducing
         return select_inducing(np.asarray(x, dtype=np.float64), min(self.m_cap, int(x.shape[0])), kernel_fn, "greedy")
 
@@ -152,8 +166,8 @@ class MatrixFreeGPModel(HasSpec):
             if int(inducing.shape[0]) > 0:
                 if self._rows(inducing, "inducing rows") > self.m_cap:
                     raise ValueError("the model was created for up to %d inducing rows, got %d" % (self.m_cap, int(inducing.shape[0])))
-                u = _lib.to_device_f64(inducing, self.device)
-        xd = _lib.to_device_f64(x, self.device)
+                u = self._scaled(_lib.to_device_f64(inducing, self.device))
+        xd = self._scaled(_lib.to_device_f64(x, self.device))
         yd = _lib.to_device_f64(y, self.device).reshape(n, -1)
         if int(yd.shape[1]) != self.ny:
             raise ValueError("y must have %d column(s), got %s" % (self.ny, tuple(yd.shape)))
@@ -188,7 +202,7 @@ class MatrixFreeGPModel(HasSpec):
         """mean [M, ny] (+ var [M] for cov='diag'): the latent function's, as in the exact model."""
         import torch
         mode = check_cov(cov)
-        xt = _lib.to_device_f64(x_test, self.device)
+        xt = self._scaled(_lib.to_device_f64(x_test, self.device))
         mt = self._rows(xt, "x_test")
         mean = torch.empty((mt, self.ny), dtype=torch.float64, device=self.device)
         var = torch.empty((mt,), dtype=torch.float64, device=self.device) if mode == _lib.COV_DIAG else None
@@ -211,17 +225,18 @@ class MatrixFreeGPModel(HasSpec):
 
 def matfree_mse_ensemble(kernel_fn, x_train, y_train, m: int, diag_reg: float = 1e-3, tol: float = 1e-10, max_iter: int = 1000,
                          rhs_cap: int = 64, chunk_rows: int = 8192, jitter: float = 1e-8, diag_reg_absolute_scale: bool = False,
-                         allow_unconverged: bool = False):
+                         allow_unconverged: bool = False, model_class=None):
     """The matrix-free counterpart of ``sparse.sparse_mse_ensemble``: a ``predict_fn(x_test=, get="nngp", compute_cov=)`` over a
     ``MatrixFreeGPModel`` fitted on all training rows with m greedy inducing rows as preconditioner.  NNGP only; compute_cov may
-    be False or "diag".  ``predict_fn.model_for("nngp")`` is the model, ``predict_fn.inducing`` the chosen indices."""
+    be False or "diag".  ``predict_fn.model_for("nngp")`` is the model, ``predict_fn.inducing`` the chosen indices.
+    ``model_class``: the model to fit, MatrixFreeGPModel (the default) or a subclass of it."""
     from .predict import Gaussian
     x_train = np.ascontiguousarray(x_train, dtype=np.float64)
     y_train = np.ascontiguousarray(y_train, dtype=np.float64).reshape(x_train.shape[0], -1)
-    model = MatrixFreeGPModel.from_kernel_fn(kernel_fn, x_train.shape[0], x_train.shape[1], m=min(int(m), x_train.shape[0]),
-                                             diag_reg=diag_reg, tol=tol, max_iter=max_iter, rhs_cap=rhs_cap, chunk_rows=chunk_rows,
-                                             jitter=jitter, diag_reg_absolute_scale=diag_reg_absolute_scale, ny=y_train.shape[1],
-                                             allow_unconverged=allow_unconverged)
+    model = (model_class or MatrixFreeGPModel).from_kernel_fn(
+        kernel_fn, x_train.shape[0], x_train.shape[1], m=min(int(m), x_train.shape[0]), diag_reg=diag_reg, tol=tol, max_iter=max_iter,
+        rhs_cap=rhs_cap, chunk_rows=chunk_rows, jitter=jitter, diag_reg_absolute_scale=diag_reg_absolute_scale, ny=y_train.shape[1],
+        allow_unconverged=allow_unconverged)
     model.fit(x_train, y_train)
 
     def model_for(get: str = "nngp") -> MatrixFreeGPModel:

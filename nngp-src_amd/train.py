@@ -60,15 +60,21 @@ def NNGP_train_and_test(args, X_train, Y_train, X_test, Y_test, query_infos_trai
     # slot pairs + the whole input; --tune_additive has tuned the kernel with its groups and brings them along
     if getattr(args, "additive", "none") == "pairs" and kernel_fn.groups is None:
         kernel_fn = kernel_fn.with_groups("pairs", full_weight=getattr(args, "additive_full_weight", 1.0))
+    # --matrix_free_groups pairs: the same table for the matrix-free model's additive form (matfree_additive.py)
+    mf_groups = getattr(args, "matrix_free_groups", "none") == "pairs"
+    if mf_groups and kernel_fn.groups is None:
+        kernel_fn = kernel_fn.with_groups("pairs", full_weight=getattr(args, "matrix_free_full_weight", 1.0))
     kernel_fn = batch(kernel_fn, device_count=0, batch_size=0)
     start = datetime.datetime.now()
     if (getattr(args, "matrix_free", 0) or 0) > 0:  # --matrix_free M: the exact posterior by PCG, M inducing rows as preconditioner
         from .matfree import matfree_mse_ensemble
+        from .matfree_additive import matfree_additive_mse_ensemble
         if args.kernel_type != "nngp":
             raise ValueError("--matrix_free solves the NNGP posterior: it needs --kernel_type nngp")
-        predict_fn = matfree_mse_ensemble(kernel_fn, X_train, Y_train, args.matrix_free, diag_reg=diag_reg,
-                                          tol=getattr(args, "matrix_free_tol", 1e-10), max_iter=getattr(args, "matrix_free_iters", 1000),
-                                          chunk_rows=getattr(args, "sparse_chunk", 8192), jitter=getattr(args, "sparse_jitter", 1e-8))
+        ensemble = matfree_additive_mse_ensemble if mf_groups else matfree_mse_ensemble
+        predict_fn = ensemble(kernel_fn, X_train, Y_train, args.matrix_free, diag_reg=diag_reg,
+                              tol=getattr(args, "matrix_free_tol", 1e-10), max_iter=getattr(args, "matrix_free_iters", 1000),
+                              chunk_rows=getattr(args, "sparse_chunk", 8192), jitter=getattr(args, "sparse_jitter", 1e-8))
     elif (getattr(args, "sparse", 0) or 0) > 0:  # --sparse M: every training row, M inducing rows (sparse.py)
         from .sparse import sparse_mse_ensemble
         if args.kernel_type != "nngp":
@@ -276,6 +282,11 @@ def make_parser():
     parser.add_argument("--matrix_free_tol", type=float, default=1e-10, metavar="T",
                         help="--matrix_free: relative residual every solve must reach")
     parser.add_argument("--matrix_free_iters", type=int, default=1000, metavar="K", help="--matrix_free: iteration limit of a solve")
+    parser.add_argument("--matrix_free_groups", type=str, default="none", choices=("none", "pairs"),
+                        help="--matrix_free on the additive kernel: 'pairs' is the table of --additive pairs inside the fused operator "
+                             "(one layer map per group and entry in every CG iteration: about G + 1 times the plain model's cost)")
+    parser.add_argument("--matrix_free_full_weight", type=float, default=1.0, metavar="W",
+                        help="--matrix_free_groups: weight of the whole-input term (0 leaves it out)")
     parser.add_argument("--tune_lr", type=float, default=0.05, help="step size of --tune_hyper")
     parser.add_argument("--b_std_init", type=float, default=None, help="start of b_std for layers with b_std = 0 (--tune_hyper)")
     return parser
@@ -283,7 +294,7 @@ def make_parser():
 
 def parse_args(argv=None):
     """The command line with its conflicts checked: --matrix_free goes with --kernel_type nngp only, and not with --sparse, --loo,
-    --tune_*, --additive or --full_cov; --sparse goes with --kernel_type nngp only, and not with --loo or --tune_*;
+    --tune_*, --additive or --full_cov (its own additive kernel is --matrix_free_groups, which needs --matrix_free); --sparse goes with --kernel_type nngp only, and not with --loo or --tune_*;
     --sparse_tune needs --sparse, --sparse_tune_ard needs both; --tune_additive needs --tune_hyper, --additive pairs, the NNGP
     and the marginal likelihood."""
     parser = make_parser()
@@ -311,6 +322,12 @@ def parse_args(argv=None):
             parser.error("argument --sparse_chunk: must be a positive multiple of 128")
     if args.matrix_free < 0:
         parser.error("argument --matrix_free: M must be >= 0")
+    if args.matrix_free_groups != "none" and args.matrix_free <= 0:
+        parser.error("argument --matrix_free_groups: needs --matrix_free M (it is the matrix-free model's additive kernel)")
+    if args.matrix_free_groups == "none" and args.matrix_free_full_weight != 1.0:
+        parser.error("argument --matrix_free_full_weight: needs --matrix_free_groups pairs")
+    if not (np.isfinite(args.matrix_free_full_weight) and args.matrix_free_full_weight >= 0.0):
+        parser.error("argument --matrix_free_full_weight: W must be finite and >= 0")
     if args.matrix_free > 0:
         if args.sparse > 0:
             parser.error("argument --matrix_free: not allowed with argument --sparse")

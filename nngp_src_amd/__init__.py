@@ -17,6 +17,8 @@ from .batching import batch  # noqa: E402,F401
 from .pool import pool_select_greedy  # noqa: E402,F401
 from .sparse import SparseGPModel, select_inducing  # noqa: E402,F401
 from .matfree import MatrixFreeGPModel, matfree_mse_ensemble  # noqa: E402,F401
+from .matfree_additive import AdditiveMatrixFreeGPModel, matfree_additive_mse_ensemble  # noqa: E402,F401
 
 __all__ = ["stax", "predict", "batch", "util", "pool_select_greedy", "SparseGPModel", "select_inducing",
-           "MatrixFreeGPModel", "matfree_mse_ensemble"]
+           "MatrixFreeGPModel", "matfree_mse_ensemble", "AdditiveMatrixFreeGPModel",
+           "matfree_additive_mse_ensemble"]
