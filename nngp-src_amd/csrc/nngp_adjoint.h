@@ -454,6 +454,24 @@ inline void trace_dk(const ArchDev& arch, const double* sq, double dn, double* t
     }
 }
 
+// dK_ii / dq_i, q_i the diagonal's q at the input of Dense layer 0: D_0 v_0 of trace_dk
+inline double diag_q_slope(const ArchDev& arch) {
+    const int nd = arch.n_dense;
+    double d0v0 = 1.0;
+    for (int l = nd - 1; l >= 0; --l) {
+        if (l < nd - 1) d0v0 *= arch.act[l] == NNGP_ACT_ABRELU ? arch.ap[l][2] : 0.5;
+        d0v0 *= arch.w2[l];
+    }
+    return d0v0;
+}
+
+// the d relevances of a caller (host): every one finite and non-negative, or rc -2 naming `who`
+inline int check_relevances(const char* who, const double* s, int d) {
+    for (int k = 0; k < d; ++k)
+        NNGP_REQUIRE(std::isfinite(s[k]) && s[k] >= 0.0, "%s: relevance %d must be finite and non-negative (%g)", who, k, s[k]);
+    return 0;
+}
+
 }  // namespace nngp
 
 namespace nngp {
@@ -520,6 +538,10 @@ int launch_by_nlc(const ArchDev& arch, int64_t nparts, const char* who, Launch l
 // k_nngp_mll_partial) and the pass with ARD set (nngp_ard.hip, k_nngp_ard_partial; a.cmat / a.qbar filled in by the caller)
 int launch_mll_partial(const MllArgs& a, const ArchDev& arch, hipStream_t s);
 int launch_ard_partial(const MllArgs& a, const ArchDev& arch, bool loo, hipStream_t s);
+// What follows the pass with ARD set, handle-free as well (nngp_ard.hip, k_ard_contract and k_ard_finish): cmat [., ldc] and
+// qbar [2][tiles per side][np] as that pass left them, x [n, d] the raw rows, part [3][tiles per side][d] scratch; out [3][d]
+int launch_ard_contract(const double* cmat, int64_t ldc, const double* x, int64_t n, int d, const double* qbar, int64_t np, double* part,
+                        double* out, hipStream_t s);
 // nngp_mll.hip: the architecture checked for the float64 gradient paths (rc -2 naming `who`), and A = K + r I (get: NNGP_GET_NNGP,
 // or NNGP_GET_NTK for Theta + r I) in w.a with the identity on the padding; red[0] = tr K, red[1] = r
 // x, q: the inputs and their row norms (the handle's own, or the scaled copy of ArdBuffers)

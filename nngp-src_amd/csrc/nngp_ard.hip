@@ -9,11 +9,11 @@
 //   k_ard_scale          xs = x o sqrt(s)  (s = 1: the bits of x)
 //   k_nngp_ard_partial   adjoint_tile with ARD set: the usual partials, S o c of the first seed into the lower triangle of zt
 //                        (dead at this point in both paths), of the matrix seed into the upper, and the per-tile sums of qbar
-//   k_ard_contract       (ard_contract.h, shared with the sparse evidence's K_uu half) the hot path: per 64-row block I,
-//                        32 features and seed, Z_I = sum_{J <= I} (S o c)[I, J] X_J on the
-//                        float64 MFMA (v_mfma_f64_16x16x4: lane l holds A[l & 15][l >> 4] and B[l >> 4][l & 15], and D at column
-//                        l & 15, row (l >> 4) + 4 reg), then sum_{i in I} x_ik (Z_ik + qbar_i x_ik), rows in order
+//   k_ard_contract       the hot path, ard_contract_body of ard_contract.h staged from the two triangles of one matrix: per
+//                        64-row block I, 32 features and seed, Z_I = sum_{J <= I} (S o c)[I, J] X_J on the float64 MFMA, then
+//                        sum_{i in I} x_ik (Z_ik + qbar_i x_ik), rows in order
 //   k_ard_finish         the row blocks summed in order
+// launch_ard_contract runs the two for the exact evidence, the leave-one-out objectives and the sparse evidence's K_uu half.
 // No atomics; every slot of qbar and of the partials has one writer.
 #include "ard_contract.h"
 #include "../../include/nngp_ard.h"
@@ -32,7 +32,45 @@ __global__ __launch_bounds__(256) void k_nngp_ard_partial(MllArgs a, ArchDev arc
     adjoint_tile<NLC, LOO, true>(a, arch);
 }
 
+// The symmetric form's staging: seed 0 at (i, j), seed 1 at (j, i) of one matrix, j < i < n = nb, every row block walking the
+// tiles up to its own; the B operand is x itself.
+struct SymStage {
+    const double *cmat, *b;
+    int64_t ldc, nb;
+    __device__ int64_t tiles(int64_t ti) const { return ti + 1; }
+    __device__ void stage(double (*ms)[MT + 1], int64_t i0, int64_t j0, int tid) const {
+        const int seed = blockIdx.z;
+        for (int e = tid; e < MT * MT; e += 256) {  // the fast index runs along memory for either seed
+            const int r = seed == 0 ? e >> 6 : e & (MT - 1), c = seed == 0 ? e & (MT - 1) : e >> 6;
+            const int64_t i = i0 + r, j = j0 + c;
+            ms[r][c] = (i < nb && j < i) ? (seed == 0 ? cmat[i * ldc + j] : cmat[j * ldc + i]) : 0.0;
+        }
+    }
+};
+
+// grid and part as ard_contract_body has them, with tn row blocks; x: the raw inputs
+__global__ __launch_bounds__(256) void k_ard_contract(const double* cmat, int64_t ldc, const double* x, int64_t n, int d,
+                                                      const double* qbar, int64_t np, int64_t tn, double* part) {
+    ard_contract_body(SymStage{cmat, x, ldc, n}, x, n, d, qbar, tn, np, tn, part);
+}
+
+// out[v * d + k] = sum over the row blocks, in order, of part[(v * tn + I) * d + k]  (v = 0, 1: the seeds; 2: sum_i x_ik^2)
+__global__ __launch_bounds__(256) void k_ard_finish(const double* part, int64_t tn, int d, double* out) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e < 3 * d) out[e] = ard_block_sum(part, tn, d, e);
+}
+
 }  // namespace
+
+int launch_ard_contract(const double* cmat, int64_t ldc, const double* x, int64_t n, int d, const double* qbar, int64_t np, double* part,
+                        double* out, hipStream_t s) {
+    const int64_t tn = (n + MT - 1) / MT;
+    const dim3 grid((unsigned)tn, (unsigned)((d + AKC - 1) / AKC), 2);
+    hipLaunchKernelGGL(k_ard_contract, grid, dim3(256), 0, s, cmat, ldc, x, n, d, qbar, np, tn, part);
+    hipLaunchKernelGGL(k_ard_finish, dim3((unsigned)((3 * d + 255) / 256)), dim3(256), 0, s, part, tn, d, out);
+    NNGP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
 
 int launch_ard_partial(const MllArgs& a, const ArchDev& arch, bool loo, hipStream_t s) {
     return launch_by_nlc(arch, a.nparts, "mll", [&](auto nlc, dim3 grid) {
@@ -46,8 +84,7 @@ int ard_begin(nngp_mll* h, const double* rel, const char* who, hipStream_t s) {
     ArdBuffers& a = h->ard;
     NNGP_REQUIRE(a.reserved, "%s: relevances need nngp_mll_reserve_ard first", who);
     const int d = h->w.d;
-    for (int k = 0; k < d; ++k)
-        NNGP_REQUIRE(std::isfinite(rel[k]) && rel[k] >= 0.0, "%s: relevance %d must be finite and non-negative (%g)", who, k, rel[k]);
+    NNGP_TRY(check_relevances(who, rel, d));
     const int64_t total = h->w.n * d;
     NNGP_HIP_CHECK(hipMemcpyAsync(a.s, rel, sizeof(double) * d, hipMemcpyHostToDevice, s));
     NNGP_HIP_CHECK(hipStreamSynchronize(s));  // rel is the caller's
@@ -67,25 +104,15 @@ int launch_ard_partial(nngp_mll* h, MllArgs a, const ArchDev& arch, bool loo, hi
 int ard_contract(nngp_mll* h, hipStream_t s) {
     ArdBuffers& a = h->ard;
     const GpWorkspace& w = h->w;
-    const int64_t tn = (w.n + MT - 1) / MT;
-    const int d = w.d;
-    const dim3 grid((unsigned)tn, (unsigned)((d + AKC - 1) / AKC), 2);
-    hipLaunchKernelGGL(k_ard_contract, grid, dim3(256), 0, s, w.zt, w.np, w.x, w.n, d, a.qbar, w.np, tn, a.part);
-    hipLaunchKernelGGL(k_ard_finish, dim3((unsigned)((3 * d + 255) / 256)), dim3(256), 0, s, a.part, tn, d, a.out);
-    NNGP_HIP_CHECK(hipGetLastError());
-    NNGP_HIP_CHECK(hipMemcpyAsync(a.host.data(), a.out, sizeof(double) * 3 * d, hipMemcpyDeviceToHost, s));
+    NNGP_TRY(launch_ard_contract(w.zt, w.np, w.x, w.n, w.d, a.qbar, w.np, a.part, a.out, s));
+    NNGP_HIP_CHECK(hipMemcpyAsync(a.host.data(), a.out, sizeof(double) * 3 * w.d, hipMemcpyDeviceToHost, s));
     return 0;
 }
 
 void ard_finish_host(nngp_mll* h, const ArchDev& arch, double diag_reg, int absolute, double s1, double s2, bool loo, double* grad_s) {
     ArdBuffers& a = h->ard;
-    const int d = h->w.d, nd = arch.n_dense;
-    const double dn = (double)h->w.n, dd = (double)d;
-    double d0v0 = 1.0;  // dK_ii / dq_i: D_0 v_0 of trace_dk
-    for (int l = nd - 1; l >= 0; --l) {
-        if (l < nd - 1) d0v0 *= arch.act[l] == NNGP_ACT_ABRELU ? arch.ap[l][2] : 0.5;
-        d0v0 *= arch.w2[l];
-    }
+    const int d = h->w.d;
+    const double dn = (double)h->w.n, dd = (double)d, d0v0 = diag_q_slope(arch);
     for (int k = 0; k < d; ++k) {
         const double trdk = d0v0 * a.host[2 * d + k] / dd;
         const double ci = absolute ? 0.0 : diag_reg * (trdk / dn);

@@ -9,15 +9,16 @@
 //   k_sparse_rect_ard_partial   rect_tile with ARD set: the layer partials as ever, kbar of the dense seed in place over D_c (dead
 //                               once read), kbar of the rank-one seed into a second buffer, and per tile the sums of qbar1 over its
 //                               columns and of qbar2 over its rows, one slot per tile
-//   k_sparse_ard_contract       the hot path: per 64-row block I of the chunk, 32 features and half, Z_I = sum_J kbar[I, J] U_J over
-//                               all inducing tiles on the float64 MFMA (v_mfma_f64_16x16x4, the operand layouts of k_ard_contract:
-//                               lane l holds A[l & 15][l >> 4] and B[l >> 4][l & 15], D at column l & 15, row (l >> 4) + 4 reg)
-//                               with the RAW U, then sum_{i in I} x_ik (Z_ik + e1_i x_ik), rows in order, and sum_{i in I} x_ik^2
-//   k_sparse_ard_finish         the row blocks summed in ascending order and added to the accumulators, chunk after chunk; likewise
-//                               e2_j += the chunk's row tiles in order
+//   k_sparse_ard_contract       the hot path, ard_contract_body of ard_contract.h (the body of k_ard_contract too) staged from the
+//                               half's dense buffer: per 64-row block I of the chunk, 32 features and half, Z_I = sum_J kbar[I, J] U_J
+//                               over all inducing tiles on the float64 MFMA with the RAW U, then sum_{i in I} x_ik (Z_ik + e1_i x_ik),
+//                               rows in order, and sum_{i in I} x_ik^2
+//   k_sparse_ard_finish         the row blocks summed in ascending order (ard_block_sum) and added to the accumulators, chunk after
+//                               chunk; likewise e2_j += the chunk's row tiles in order
 // and once per call: the symmetric half over K_uu (launch_ard_partial of nngp_ard.hip, k_nngp_ard_partial<NLC, false>, seeded with
-// gamma and E, then k_ard_contract of ard_contract.h with the raw U), and k_sparse_ard_cols, sum_j e2_j u_jk^2.  No float atomics, no device-side counter, no workgroup
-// waits for another: launch boundaries are the only synchronisation, every slot has one writer and every sum a fixed order.
+// gamma and E, then launch_ard_contract with the raw U), and k_sparse_ard_cols, sum_j e2_j u_jk^2.  No float atomics, no
+// device-side counter, no workgroup waits for another: launch boundaries are the only synchronisation, every slot has one writer
+// and every sum a fixed order.
 #include "ard_contract.h"
 #include "sparse_rect.h"
 #include "sparse_gp.h"
@@ -38,71 +39,27 @@ __global__ __launch_bounds__(256) void k_sparse_rect_ard_partial(RectArgs a, Arc
     rect_tile<NLC, true>(a, arch);
 }
 
-// grid (row blocks of the chunk, feature chunks, 2 halves).  kb0 / kb1: [c, ld] kbar of the rank-one / the dense seed; x: [c, d] and
-// u: [m, d] the raw rows; qrow: RectArgs::qrow.  part[(half * tb + I) * d + k]; half 0 also writes
-// part[(2 tb + I) * d + k] = sum_{i in I} x_ik^2.
-__global__ __launch_bounds__(256) void k_sparse_ard_contract(const double* kb0, const double* kb1, int64_t ld, const double* x, int64_t c,
-                                                             const double* u, int64_t m, int d, const double* qrow, int64_t cp,
-                                                             int64_t tu, int64_t tb, double* part) {
-    __shared__ double ms[MT][MT + 1];
-    __shared__ double xt[MT][AKC + 1];
-    __shared__ double qb[MT];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, lr = lane & 15, lk = lane >> 4;
-    const int64_t ti = blockIdx.x, i0 = ti * MT;
-    const int k0 = blockIdx.y * AKC, half = blockIdx.z;
-    const double* cm = half == 0 ? kb0 : kb1;
-    if (tid < MT) {  // e1 of the block's rows: the column tiles' slots in order
-        double t = 0.0;
-        for (int64_t sl = 0; sl < tu; ++sl) t += qrow[((int64_t)half * tu + sl) * cp + i0 + tid];
-        qb[tid] = t;
-    }
-    v4d acc[2] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
-    for (int64_t tj = 0; tj < tu; ++tj) {
-        const int64_t j0 = tj * MT;
+// The rectangular form's staging: either half reads its own dense [c, ld] buffer, kb0 kbar of the rank-one and kb1 of the dense
+// seed, every row block walking all tu inducing tiles; the B operand is the raw u.
+struct RectStage {
+    const double *cm, *b;
+    int64_t ld, c, tu, nb;
+    __device__ int64_t tiles(int64_t) const { return tu; }
+    __device__ void stage(double (*ms)[MT + 1], int64_t i0, int64_t j0, int tid) const {
         for (int e = tid; e < MT * MT; e += 256) {
             const int r = e >> 6, cc = e & (MT - 1);
             const int64_t i = i0 + r, j = j0 + cc;
-            ms[r][cc] = (i < c && j < m) ? cm[i * ld + j] : 0.0;
+            ms[r][cc] = (i < c && j < nb) ? cm[i * ld + j] : 0.0;
         }
-        for (int e = tid; e < MT * AKC; e += 256) {
-            const int cc = e / AKC, k = e % AKC;
-            const int64_t j = j0 + cc;
-            xt[cc][k] = (j < m && k0 + k < d) ? u[j * d + k0 + k] : 0.0;
-        }
-        __syncthreads();
-#pragma unroll 4
-        for (int kk = 0; kk < MT; kk += 4) {
-            const double av = ms[16 * wv + lr][kk + lk];
-            acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, xt[kk + lk][lr], acc[0], 0, 0, 0);
-            acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, xt[kk + lk][16 + lr], acc[1], 0, 0, 0);
-        }
-        __syncthreads();
     }
-    for (int e = tid; e < MT * AKC; e += 256) {  // the block's own rows of x
-        const int cc = e / AKC, k = e % AKC;
-        const int64_t i = i0 + cc;
-        xt[cc][k] = (i < c && k0 + k < d) ? x[i * d + k0 + k] : 0.0;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int hb = 0; hb < 2; ++hb)
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-            const int r = 16 * wv + lk + 4 * reg, cc = 16 * hb + lr;
-            const double xv = xt[r][cc];
-            ms[r][cc] = xv * (acc[hb][reg] + qb[r] * xv);
-        }
-    __syncthreads();
-    if (tid < AKC) {
-        double t = 0.0;
-        for (int r = 0; r < MT; ++r) t += ms[r][tid];
-        if (k0 + tid < d) part[((int64_t)half * tb + ti) * d + k0 + tid] = t;
-    } else if (tid < 2 * AKC && half == 0) {
-        const int k = tid - AKC;
-        double t = 0.0;
-        for (int r = 0; r < MT; ++r) t += xt[r][k] * xt[r][k];
-        if (k0 + k < d) part[((int64_t)2 * tb + ti) * d + k0 + k] = t;
-    }
+};
+
+// grid and part as ard_contract_body has them, with the chunk's tb row blocks and a half per seed.  x: [c, d] and u: [m, d] the
+// raw rows; qrow: RectArgs::qrow.
+__global__ __launch_bounds__(256) void k_sparse_ard_contract(const double* kb0, const double* kb1, int64_t ld, const double* x, int64_t c,
+                                                             const double* u, int64_t m, int d, const double* qrow, int64_t cp,
+                                                             int64_t tu, int64_t tb, double* part) {
+    ard_contract_body(RectStage{blockIdx.z == 0 ? kb0 : kb1, u, ld, c, tu, m}, x, c, d, qrow, tu, cp, tb, part);
 }
 
 // acc[v * d + k] += sum over the chunk's row blocks, in order, of part[(v * tb + I) * d + k]   (v = 0, 1: the halves; 2: sum x_ik^2)
@@ -111,10 +68,7 @@ __global__ __launch_bounds__(256) void k_sparse_ard_finish(const double* part, i
                                                            int64_t m, double* acc, double* e2) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e < 3 * (int64_t)d) {
-        const int64_t v = e / d, k = e % d;
-        double t = 0.0;
-        for (int64_t b = 0; b < tb; ++b) t += part[(v * tb + b) * d + k];
-        acc[e] += t;
+        acc[e] += ard_block_sum(part, tb, d, e);
     } else if (e < 3 * (int64_t)d + 2 * m) {
         const int64_t f = e - 3 * (int64_t)d, hf = f / m, j = f % m;
         double t = 0.0;
@@ -170,12 +124,6 @@ int launch_scale(const double* x, const double* sq, int64_t rows, int d, double*
     return 0;
 }
 
-void drop_fit(nngp_sparse* h) {
-    h->m = h->mp = h->n = h->chunks = 0;
-    h->finished = h->have_terms = h->have_ard_terms = false;
-    h->sigma2 = 0.0;
-}
-
 }  // namespace
 
 int sparse_ard_scale(const nngp_sparse* h, const double* x, int64_t rows, double* out, hipStream_t s) {
@@ -188,15 +136,11 @@ int sparse_ard_begin(nngp_sparse* h, hipStream_t s) {
 }
 
 int sparse_ard_uu(nngp_sparse* h, const double* seed, const double* gamma, double* cmat, hipStream_t s) {
-    const int64_t m = h->m, mp = h->mp, tn = (m + MT - 1) / MT;
+    const int64_t m = h->m, mp = h->mp;
     const int d = h->d;
     MllArgs ma{h->u, h->uq, m, d, seed, mp, gamma, nullptr, h->ev_part, gp_lower_tiles(m), cmat, mp, h->ard_qbar, mp};
     NNGP_TRY(launch_ard_partial(ma, h->arch, false, s));
-    const dim3 grid((unsigned)tn, (unsigned)((d + AKC - 1) / AKC), 2);
-    hipLaunchKernelGGL(k_ard_contract, grid, dim3(256), 0, s, cmat, mp, h->ard_u, m, d, h->ard_qbar, mp, tn, h->ard_part);
-    hipLaunchKernelGGL(k_ard_finish, dim3((unsigned)((3 * d + 255) / 256)), dim3(256), 0, s, h->ard_part, tn, d, h->ard_acc + 5 * d);
-    NNGP_HIP_CHECK(hipGetLastError());
-    return 0;
+    return launch_ard_contract(cmat, mp, h->ard_u, m, d, h->ard_qbar, mp, h->ard_part, h->ard_acc + 5 * d, s);
 }
 
 int sparse_ard_chunk(nngp_sparse* h, const double* x_raw, const double* xs, int64_t c, const double* beta, const double* gamma,
@@ -215,15 +159,9 @@ int sparse_ard_end(nngp_sparse* h, hipStream_t s) {
 }
 
 void sparse_ard_finish_host(nngp_sparse* h, bool vfe, double s2, double ts, double bb, double gg, double* grad_s) {
-    const ArchDev& arch = h->arch;
-    const int d = h->d, nd = arch.n_dense;
-    const double dn = (double)h->n, dm = (double)h->m, dd = (double)d;
+    const int d = h->d;
+    const double dn = (double)h->n, dm = (double)h->m, dd = (double)d, d0v0 = diag_q_slope(h->arch);
     const double* v = h->ard_host.data();
-    double d0v0 = 1.0;  // dK_ii / dq_i: D_0 v_0 of trace_dk
-    for (int l = nd - 1; l >= 0; --l) {
-        if (l < nd - 1) d0v0 *= arch.act[l] == NNGP_ACT_ABRELU ? arch.ap[l][2] : 0.5;
-        d0v0 *= arch.w2[l];
-    }
     double* t = h->ard_terms.data();
     for (int k = 0; k < d; ++k) {
         const double trdk_f = d0v0 * v[2 * d + k] / dd, trdk_u = d0v0 * v[7 * d + k] / dd;
@@ -292,22 +230,19 @@ int nngp_sparse_reserve_ard(nngp_sparse* h) {
 
 int nngp_sparse_set_relevance(nngp_sparse* h, const double* s) {
     NNGP_REQUIRE(h != nullptr, "sparse_set_relevance: NULL argument");
-    if (s == nullptr) {
-        h->have_rel = false;
-        drop_fit(h);
-        return 0;
-    }
-    NNGP_REQUIRE(h->ard_reserved, "sparse_set_relevance: relevances need nngp_sparse_reserve_ard first");
     const int d = h->d;
-    for (int k = 0; k < d; ++k)
-        NNGP_REQUIRE(std::isfinite(s[k]) && s[k] >= 0.0, "sparse_set_relevance: relevance %d must be finite and non-negative (%g)", k, s[k]);
+    if (s != nullptr) {
+        NNGP_REQUIRE(h->ard_reserved, "sparse_set_relevance: relevances need nngp_sparse_reserve_ard first");
+        NNGP_TRY(check_relevances("sparse_set_relevance", s, d));
+    }
+    h->have_rel = h->have_ard_terms = false;
+    sparse_drop_fit(h);
+    if (s == nullptr) return 0;
     std::vector<double> both((size_t)(2 * d));
     for (int k = 0; k < d; ++k) {
         both[k] = s[k];
         both[d + k] = std::sqrt(s[k]);
     }
-    h->have_rel = false;
-    drop_fit(h);
     NNGP_HIP_CHECK(hipDeviceSynchronize());  // earlier work may still read the old values
     NNGP_HIP_CHECK(hipMemcpy(h->ard_s, both.data(), sizeof(double) * 2 * d, hipMemcpyHostToDevice));
     h->have_rel = true;
@@ -339,46 +274,33 @@ int nngp_sparse_ard_rect(const double* x, int64_t c, const double* u, int64_t m,
                  "sparse_ard_rect: NULL argument");
     NNGP_REQUIRE(c >= 1 && m >= 1 && d >= 1 && ld >= m, "sparse_ard_rect: need c, m, d >= 1 and ld >= m (c=%lld m=%lld d=%d ld=%lld)",
                  (long long)c, (long long)m, d, (long long)ld);
-    for (int k = 0; k < d; ++k)
-        NNGP_REQUIRE(std::isfinite(s_host[k]) && s_host[k] >= 0.0, "sparse_ard_rect: relevance %d must be finite and non-negative (%g)", k,
-                     s_host[k]);
+    NNGP_TRY(check_relevances("sparse_ard_rect", s_host, d));
     ArchDev ad{};
     NNGP_TRY(mll_make_arch(arch, 0.0, "sparse_ard_rect", &ad));
     const int64_t tu = (m + MT - 1) / MT, tr = (c + MT - 1) / MT, tiles = tr * tu, cp = tr * MT, mpc = tu * MT;
     const int64_t n4 = 4 * ad.n_dense, dd = d;
     std::vector<double> sq((size_t)d), res((size_t)(5 * dd));
     for (int k = 0; k < d; ++k) sq[k] = std::sqrt(s_host[k]);
-    // sqrt(s) | xs | us | xq | uq | kbar (dense seed) | kbar (rank-one seed) | qrow | qcol | layer partials | part | acc, e2
-    const int64_t sizes[12] = {dd, c * dd, m * dd, c, m, c * m, c * m, 2 * tu * cp, 2 * tr * mpc, n4 * tiles, 3 * tr * dd, 8 * dd + 2 * mpc};
-    int64_t total = 0;
-    for (int64_t v : sizes) total += v;
-    double* buf = nullptr;
-    NNGP_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&buf), sizeof(double) * total, s));
-    double* p[12];
-    p[0] = buf;
-    for (int e = 1; e < 12; ++e) p[e] = p[e - 1] + sizes[e - 1];
-    double *dsq = p[0], *xs = p[1], *us = p[2], *xq = p[3], *uq = p[4], *kbi = p[5], *kba = p[6], *qrow = p[7], *qcol = p[8], *lpart = p[9],
-           *part = p[10], *acc = p[11];
-    int rc = 0;
-    if (hipMemcpyAsync(dsq, sq.data(), sizeof(double) * d, hipMemcpyHostToDevice, s) != hipSuccess) rc = -1;
-    if (rc == 0) rc = launch_scale(x, dsq, c, d, xs, s);
-    if (rc == 0) rc = launch_scale(u, dsq, m, d, us, s);
-    if (rc == 0) rc = launch_row_sqnorm(xs, c, d, xq, s);
-    if (rc == 0) rc = launch_row_sqnorm(us, m, d, uq, s);
-    if (rc == 0 && hipMemcpy2DAsync(kbi, sizeof(double) * m, seed, sizeof(double) * ld, sizeof(double) * m, (size_t)c,
-                                    hipMemcpyDeviceToDevice, s) != hipSuccess)
-        rc = -1;
-    if (rc == 0 && hipMemsetAsync(acc, 0, sizeof(double) * (8 * dd + 2 * mpc), s) != hipSuccess) rc = -1;
-    if (rc == 0) {
+    // kbi: the dense seed, then its kbar; kba: kbar of the rank-one seed; lpart: the layer partials; acc: the sums, then e2
+    double *dsq, *xs, *us, *xq, *uq, *kbi, *kba, *qrow, *qcol, *lpart, *part, *acc;
+    const auto work = [&]() -> int {
+        NNGP_HIP_CHECK(hipMemcpyAsync(dsq, sq.data(), sizeof(double) * d, hipMemcpyHostToDevice, s));
+        NNGP_TRY(launch_scale(x, dsq, c, d, xs, s));
+        NNGP_TRY(launch_scale(u, dsq, m, d, us, s));
+        NNGP_TRY(launch_row_sqnorm(xs, c, d, xq, s));
+        NNGP_TRY(launch_row_sqnorm(us, m, d, uq, s));
+        NNGP_HIP_CHECK(hipMemcpy2DAsync(kbi, sizeof(double) * m, seed, sizeof(double) * ld, sizeof(double) * m, (size_t)c,
+                                        hipMemcpyDeviceToDevice, s));
+        NNGP_HIP_CHECK(hipMemsetAsync(acc, 0, sizeof(double) * (8 * dd + 2 * mpc), s));
         RectArgs ra{xs, xq, c, us, uq, m, d, kbi, m, beta, gamma, lpart, tiles, tu, kbi, kba, qrow, cp, qcol, tr, mpc};
-        rc = rect_ard_block(ra, ad, x, u, part, acc, acc + 8 * dd, s);
-    }
-    if (rc == 0) rc = launch_cols(acc + 8 * dd, mpc, u, m, d, acc + 3 * dd, s);
-    if (rc == 0 && hipMemcpyAsync(res.data(), acc, sizeof(double) * 5 * dd, hipMemcpyDeviceToHost, s) != hipSuccess) rc = -1;
-    (void)hipFreeAsync(buf, s);
-    NNGP_HIP_CHECK(hipStreamSynchronize(s));
-    if (rc == -1) set_error("sparse_ard_rect: a HIP call failed");
-    if (rc != 0) return rc;
+        NNGP_TRY(rect_ard_block(ra, ad, x, u, part, acc, acc + 8 * dd, s));
+        NNGP_TRY(launch_cols(acc + 8 * dd, mpc, u, m, d, acc + 3 * dd, s));
+        NNGP_HIP_CHECK(hipMemcpyAsync(res.data(), acc, sizeof(double) * 5 * dd, hipMemcpyDeviceToHost, s));
+        return 0;
+    };
+    NNGP_TRY(with_stream_block(s, {{&dsq, dd}, {&xs, c * dd}, {&us, m * dd}, {&xq, c}, {&uq, m}, {&kbi, c * m}, {&kba, c * m},
+                                   {&qrow, 2 * tu * cp}, {&qcol, 2 * tr * mpc}, {&lpart, n4 * tiles}, {&part, 3 * tr * dd},
+                                   {&acc, 8 * dd + 2 * mpc}}, work));
     for (int k = 0; k < d; ++k) {
         out[k] = (res[k] + res[3 * dd + k]) / (double)d;
         out[d + k] = (res[dd + k] + res[4 * dd + k]) / (double)d;

@@ -219,9 +219,7 @@ int nngp_sparse_set_kernel(nngp_sparse* h, const nngp_arch_act* arch, double dia
     h->arch = ad;
     h->diag_reg = diag_reg;
     h->absolute = diag_reg_absolute_scale != 0;
-    h->m = h->mp = h->n = h->chunks = 0;
-    h->finished = h->have_terms = false;
-    h->sigma2 = 0.0;
+    sparse_drop_fit(h);
     return 0;
 }
 
@@ -407,25 +405,17 @@ int nngp_sparse_adjoint_rect(const double* x, int64_t c, const double* u, int64_
     NNGP_TRY(mll_make_arch(arch, 0.0, "sparse_adjoint_rect", &ad));
     const int n4 = 4 * ad.n_dense;
     const int64_t tu = (m + MT - 1) / MT, tiles = ((c + MT - 1) / MT) * tu;
-    double* buf = nullptr;  // xq | uq | acc | part
-    NNGP_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&buf), sizeof(double) * (c + m + n4 + n4 * tiles), s));
-    double* xq = buf;
-    double* uq = xq + c;
-    double* acc = uq + m;
-    double* part = acc + n4;
-    int rc = launch_row_sqnorm(x, c, d, xq, s);
-    if (rc == 0) rc = launch_row_sqnorm(u, m, d, uq, s);
-    if (rc == 0 && hipMemsetAsync(acc, 0, sizeof(double) * n4, s) != hipSuccess) rc = -1;
-    if (rc == 0) {
+    double *xq, *uq, *acc, *part;
+    return with_stream_block(s, {{&xq, c}, {&uq, m}, {&acc, n4}, {&part, n4 * tiles}}, [&]() -> int {
+        NNGP_TRY(launch_row_sqnorm(x, c, d, xq, s));
+        NNGP_TRY(launch_row_sqnorm(u, m, d, uq, s));
+        NNGP_HIP_CHECK(hipMemsetAsync(acc, 0, sizeof(double) * n4, s));
         RectArgs ra{x, xq, c, u, uq, m, d, seed, ld, beta, gamma, part, tiles, tu};
-        rc = launch_rect(ra, ad, s);
-    }
-    if (rc == 0) rc = reduce_into(part, tiles, n4, acc, s);
-    if (rc == 0 && hipMemcpyAsync(out, acc, sizeof(double) * n4, hipMemcpyDeviceToHost, s) != hipSuccess) rc = -1;
-    (void)hipFreeAsync(buf, s);
-    NNGP_HIP_CHECK(hipStreamSynchronize(s));
-    if (rc == -1) set_error("sparse_adjoint_rect: a HIP call failed");
-    return rc;
+        NNGP_TRY(launch_rect(ra, ad, s));
+        NNGP_TRY(reduce_into(part, tiles, n4, acc, s));
+        NNGP_HIP_CHECK(hipMemcpyAsync(out, acc, sizeof(double) * n4, hipMemcpyDeviceToHost, s));
+        return 0;
+    });
 }
 
 }  // extern "C"

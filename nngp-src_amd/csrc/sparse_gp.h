@@ -3,6 +3,8 @@
 #pragma once
 #include "gp_f64.h"
 
+#include <initializer_list>
+#include <utility>
 #include <vector>
 
 // slots of nngp_sparse::scal.  [0, 4) are the fit's own; the rest belongs to the evidence (include/nngp_sparse_evidence.h)
@@ -85,6 +87,31 @@ struct nngp_sparse {
 };
 
 namespace nngp {
+// What a new kernel or new relevances leave of a fit: no inducing set, no rows, no evidence terms
+inline void sparse_drop_fit(nngp_sparse* h) {
+    h->m = h->mp = h->n = h->chunks = 0;
+    h->finished = h->have_terms = false;
+    h->sigma2 = 0.0;
+}
+// For the stand-alone entry points that own no handle: one stream-ordered block of doubles carved into the named pieces (one
+// hipMallocAsync, every pointer set), work() queued on s, and on the way out, whatever work returned, the block freed behind it
+// and s synchronised.
+template <class Work>
+int with_stream_block(hipStream_t s, std::initializer_list<std::pair<double**, int64_t>> pieces, Work work) {
+    int64_t total = 0;
+    for (const auto& p : pieces) total += p.second;
+    double* buf = nullptr;
+    NNGP_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&buf), sizeof(double) * total, s));
+    double* next = buf;
+    for (const auto& p : pieces) {
+        *p.first = next;
+        next += p.second;
+    }
+    const int rc = work();
+    (void)hipFreeAsync(buf, s);
+    NNGP_HIP_CHECK(hipStreamSynchronize(s));
+    return rc;
+}
 // sparse_gp.hip.  out [rp, mp] <- K(x [rows, d], U) L_u^-T: zero, cross build, solve in place (rp = rows rounded up to 128);
 // skip & 1 leaves out the build, skip & 2 the solve (then out = K(x, U), zero beyond rows and m)
 int sparse_cross(nngp_sparse* h, const double* x, const double* xq, int64_t rows, double* out, hipStream_t s, int skip = 0);
